@@ -24,6 +24,12 @@
 Tables are built and resident in HBM before the timed region.  Multi-GPU: one process per GPU
 (torch.distributed.run); no data-path collective (gloo only times it).
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does
+not need: the CPU baseline (the oracle on the host cores, 3 x 20 s; cpu_baseline) and the board power / clock
+samples over the timed region (roofline.power); without it both are null / marked unavailable.
+--dump-outputs DIR writes what the timed search returned as DIR/<name>.npy (float64) after the timed steps: the
+level-1 candidates of the last timed step, the keys found and the device's counts (dump_outputs).
+
 Prints ONE JSON line (rank 0).  See DESIGN.md §5-§6 for the roofline definitions.
 """
 from __future__ import annotations
@@ -156,6 +162,8 @@ def cpu_baseline(seconds: float, threads: int, target, base: int):
 def power_sampler(torch, local: int, args):
     """Board power / clock sampler over the timed region (keyhuntm1cpu_amd/power.py; amdsmi, not HIP)."""
     from keyhuntm1cpu_amd.power import PowerSampler
+    if not args.full:
+        return PowerSampler.disabled("not sampled: a plain run (pass --full)")
     if args.no_power:
         return PowerSampler.disabled("--no-power")
     bdf = physical_gpu(torch, local)                   # "dddd:bb:dd" (full domain:bus:device, ADVICE r5)
@@ -202,6 +210,24 @@ def lib_record(args) -> dict:
     rel = lambda p: os.path.relpath(p, REPO) if p.startswith(REPO + os.sep) else p   # noqa: E731
     return {"lib_sha16": info["sha16"], "lib_path": rel(info["path"]), "host_lib_sha16": host_sha,
             "host_lib_path": rel(host_path), "build": {k: v for k, v in info.items() if k not in ("sha16", "path")}}
+
+
+def key_limbs(found) -> "list[list[float]]":
+    """One row per found-or-not key: 1.0 / 0.0, then the 256-bit key as eight 32-bit limbs, most significant first
+    (every entry exact in float64)."""
+    return [[0.0 if k is None else 1.0] + [float(((k or 0) >> (32 * (7 - i))) & 0xFFFFFFFF) for i in range(8)]
+            for k in found]
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy, float64, for every array of what the timed search returned.  The run's inputs
+    are fixed by its arguments (the puzzle's public key or target file and the static range partition; nothing is
+    drawn at random), so two builds run with the same arguments can be compared array for array.  The arrays are a few
+    kilobytes: every value is an integer below 2^53, exact in float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, (rows, width) in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(rows, dtype=np.float64).reshape(-1, width))
 
 
 def init_gloo(dist, rank: int, world: int):
@@ -252,13 +278,21 @@ def main():
                          "eight work items (4096 at k=1, 16384 at k=4), as the CLI's auto batch does "
                          "(engine.cpp batch_chunks)")
     ap.add_argument("--k", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline) and the "
+                         "board power / clock samples over the timed region (roofline.power).  Off by default: a plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed search returned as DIR/<name>.npy (float64): "
+                         "candidates (the last timed step's level-1 candidates), found, counts; see dump_outputs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
-                    help="CPU-baseline window after the table build (default 3 windows of 20 s: SURVEY.md section 8d's "
-                         "60 s, with the spread between windows)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: CPU-baseline window after the table build (default 3 windows of 20 s: SURVEY.md "
+                         "section 8d's 60 s, with the spread between windows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-windows", type=int, default=3,
-                    help="repeat the CPU-baseline window this many times and report the mean and spread")
-    ap.add_argument("--no-power", action="store_true", help="do not sample board power during the timed region")
+                    help="--full: repeat the CPU-baseline window this many times and report the mean and spread")
+    ap.add_argument("--no-power", action="store_true",
+                    help="--full without the board power samples during the timed region")
     ap.add_argument("--share-gpus", action="store_true",
                     help="allow more ranks than visible GPUs (a multi-rank rehearsal: ranks share GPUs round-robin "
                          "and the line says so in config.physical_gpus / gpus_shared); refused otherwise")
@@ -276,6 +310,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check-fail", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = True                # the CPU baseline is --full's (as the power samples, power_sampler)
     check_lib_dir(args)
     if args.workload == "p130" and args.k != 1:
         raise SystemExit("--workload p130 is BASELINE configs[3]: k = 1")
@@ -381,8 +417,9 @@ def main():
                 % (line[:16], world))
         cpu_base = lo
     sess = khhost.Session(tables, devices=[local], chunks_per_batch=args.chunks, check_threads=host_threads)
-    if args.no_gate:
-        sess.set_test_hooks(use_gate=False)
+    if args.no_gate or args.dump_outputs:
+        # --dump-outputs: the session also keeps the launches' level-1 candidates (a few per step)
+        sess.set_test_hooks(use_gate=not args.no_gate, record=bool(args.dump_outputs))
     sess.set_check_mode({"host": khhost.CHECK_HOST, "gpu": khhost.CHECK_DEVICE, "auto": khhost.CHECK_AUTO}[args.check])
 
     def sync():
@@ -403,6 +440,17 @@ def main():
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what the timed call returned: the keys found and the device's counts over the timed steps, and of the
+        # launches' candidates those of the last timed step (its chunks' index in the timed region, target, giant
+        # step a), sorted: the launches append them in the order their waves finish
+        last = (args.steps - 1) * args.chunks
+        cands = sorted(((b - tstart) // two_n, tg, a) for b, tg, a in sess.recorded())
+        sfx = "_rank%d" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs, {
+            "candidates" + sfx: ([c for c in cands if c[0] >= last], 3),
+            "found" + sfx: (key_limbs(res), 9),
+            "counts" + sfx: ([st[k] for k in ("chunks", "giant_steps", "candidates", "degenerate")], 4)})
     sess.close()
     steps_done = st["giant_steps"]               # counted on the device (khb_collect, count_walked)
     psum = sampler.summary(work_units=steps_done, seconds=dt)
@@ -663,6 +711,14 @@ def bench_address(args, world, rank, dist, torch, lib_rec):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what the timed call returned: the keys found (sorted: discovery order follows the launches' waves), each
+        # with its compressed flag, and the device's counts over the timed steps
+        sfx = "_rank%d" % rank if world > 1 else ""
+        hits = sorted((k, c) for k, c, _ in found)
+        dump_outputs(args.dump_outputs, {
+            "found" + sfx: ([row + [float(c)] for row, (_, c) in zip(key_limbs([k for k, _ in hits]), hits)], 10),
+            "counts" + sfx: ([st[k] for k in ("chunks", "keys", "hits", "degenerate")], 4)})
     keys = st["keys"]
     bad = 0.0 if keys == args.steps * chunks * n_seq else 1.0
     tot, tmax, mhz = float(keys), dt, st["shader_mhz"]

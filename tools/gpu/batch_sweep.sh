@@ -9,7 +9,7 @@ mkdir -p $O
 for r in 1 2; do
   for c in 4096 2048 1024; do
     echo "[$(date +%T)] round $r chunks $c"
-    timeout -k 10 180 python3 -u bench.py --steps $((81920 / c)) --warmup 5 --chunks $c --no-cpu-baseline > $O/c${c}_$r.json 2> $O/c${c}_$r.err || exit 1
+    timeout -k 10 180 python3 -u bench.py --steps $((81920 / c)) --warmup 5 --chunks $c --full --no-cpu-baseline > $O/c${c}_$r.json 2> $O/c${c}_$r.err || exit 1
   done
 done
 for f in $O/c*.json; do python3 -c "

@@ -54,7 +54,7 @@ fi
 
 if has address; then
 step address bench
-timeout -k 10 300 python3 bench.py --workload address --steps 3 --warmup 1 --cpu-seconds 20 > $O/bench_address.json 2> $O/bench_address.err || exit 1
+timeout -k 10 300 python3 bench.py --workload address --steps 3 --warmup 1 --full --cpu-seconds 20 > $O/bench_address.json 2> $O/bench_address.err || exit 1
 cat $O/bench_address.json
 if [ -f $W ]; then
   for lib in $L $W; do
