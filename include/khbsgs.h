@@ -48,7 +48,11 @@ extern "C" {
  * any other call (khb_stats gained launch_begin_ms/launch_end_ms/shader_mhz in ABI 3 and 4; ABI 5 added
  * khb_load_check_tables / khb_check; ABI 6 added khb_stats.event_ms; ABI 7 added khb_build_info,
  * khb_set_gate_stage0 / khb_gate_stages, KHB_EHANDOFF / khb_last_handoff and the -m address endomorphism
- * (KHB_SEARCH_ENDOMORPHISM, khb_addr_hit.kind = form | e << 2)). */
+ * (KHB_SEARCH_ENDOMORPHISM, khb_addr_hit.kind = form | e << 2)).  The resident level-1 bloom and gate
+ * (khb_build_l1_resident, khb_mem_info, khb_resident_bytes / khb_resident_read / khb_resident_popcount and
+ * khb_gate_probe) are additions to ABI 7: no existing signature or struct changed, so the version stays 7 (a bench
+ * line's build record, which tests/test_launch.py pins to "7", keeps naming the same scan ABI); a caller that needs
+ * them checks for the khb_build_l1_resident symbol. */
 #define KHB_ABI_VERSION 7
 int khb_abi_version(void);
 /* What this library was built as, one line of `key=value` words: abi, arch, variant ("product" for the in-tree
@@ -305,6 +309,44 @@ int khb_build_baby(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, 
                    uint64_t l1ext, uint64_t m2, uint64_t m3, const uint64_t bytes_per_sub[3],
                    const uint64_t bits_per_sub[3], const uint32_t hashes[3], uint8_t* l1, uint8_t* l2, uint8_t* l3,
                    uint8_t* bp, uint8_t* gate, uint32_t gate_log2, uint32_t gate_probes, float* kernel_ms);
+
+/* ---- resident level-1 bloom and gate (additions to ABI 7): large -k, where the level-1 bloom is tens of GB ----
+ * The same walk as khb_build_baby over the loaded giant table (Gn) and lane offsets, for the level-1 bloom and its
+ * gate alone: every x with ic < l1ext is added to both, and they STAY on the device, installed as the context's
+ * bloom and gate exactly as if khb_load_bloom and khb_load_gate had been called with the same bytes (the stage-1
+ * fold, the stage-0 filter and the one-probe hi-word fill of khb_load_gate are made by device kernels, under the
+ * same khb_set_gate_stage1 / khb_set_gate_stage0 rules).  Nothing of size O(L1) or O(gate) crosses PCIe or touches
+ * host memory.  The bloom is written directly in the layout the probe reads (256 sub-blooms of bytes_per_sub bytes
+ * concatenated; a 32-bit word may straddle two sub-blooms), so there is no second device copy and no repack pass:
+ * peak device memory of a build is L1 (256 x bytes_per_sub) + the gate (2^gate_log2 / 8) + its fold and filter
+ * + slot 0's prefix scratch (khb_reserve_slots).
+ * gate_log2: 0 = no gate, otherwise in [13, 38]: 38 is the most the 32-bit block index x mod 2^32 addresses
+ * (2^32 blocks, 32 GiB).  A build replaces any bloom or gate already installed (on failure none is installed);
+ * KHB_EBUSY while a submission is in flight.  Load the search's giant table and lane offsets afterwards. */
+int khb_build_l1_resident(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, uint32_t groups_per_job,
+                          uint64_t l1ext, uint64_t bytes_per_sub, uint64_t bits_per_sub, uint32_t hashes,
+                          uint32_t gate_log2, uint32_t gate_probes, float* kernel_ms);
+
+/* The device's free and total memory now, and the bytes of one submission slot's prefix scratch at this context's
+ * lane count (any pointer may be NULL): what a caller sizes a resident gate by. */
+int khb_mem_info(khb_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes, uint64_t* slot_bytes);
+
+/* Inspection of the installed tables (synchronous; for parity tests and measurement), whether khb_load_* or
+ * khb_build_l1_resident installed them.  KHB_ESTATE when the table is not installed. */
+#define KHB_TABLE_L1 0       /* level-1 bloom: 256 sub-blooms concatenated */
+#define KHB_TABLE_GATE 1     /* level-0 gate as the device holds it (one probe: every block's hi word set) */
+#define KHB_TABLE_FOLD 2     /* its stage-1 fold */
+#define KHB_TABLE_STAGE0 3   /* the stage-0 filter */
+/* Size of the table in bytes (0 when it is not installed). */
+int khb_resident_bytes(const khb_ctx* ctx, int which, uint64_t* bytes);
+/* Copy bytes [offset, offset + bytes) of the table to out. */
+int khb_resident_read(khb_ctx* ctx, int which, uint64_t offset, uint64_t bytes, uint8_t* out);
+/* Bits set in the table (a grid-stride reduction on the device). */
+int khb_resident_popcount(khb_ctx* ctx, int which, uint64_t* bits_set);
+/* The gate's counterpart of khb_probe for 32-byte BE x values, through the scan's own device functions: out[i]
+ * bit 0 = the full gate passes x, bit 1 = the stage-1 fold passes (1 when there is none), bit 2 = the stage-0
+ * filter passes (1 when there is none).  KHB_ESTATE without a gate. */
+int khb_gate_probe(khb_ctx* ctx, const uint8_t* xs, uint8_t* out, uint32_t n);
 
 #ifdef __cplusplus
 }

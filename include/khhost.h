@@ -18,8 +18,9 @@ extern "C" {
 #endif
 
 /* ABI version of this header; bumped whenever a signature, a struct or an output array changes.
- * A binding checks khh_abi_version() == the KHH_ABI_VERSION it was written for before any other call. */
-#define KHH_ABI_VERSION 6
+ * A binding checks khh_abi_version() == the KHH_ABI_VERSION it was written for before any other call.
+ * ABI 7 added resident tables (large -k): khh_tables_new_resident and the khh_session_resident_* calls. */
+#define KHH_ABI_VERSION 7
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -38,6 +39,24 @@ khh_tables* khh_tables_new_files(const char* n_str, int k, int threads, uint32_t
  * *kernel_ms (nullable) receives the build kernel's time. */
 khh_tables* khh_tables_new_gpu(const char* n_str, int k, int threads, uint32_t gpl, int device, double* kernel_ms,
                                char* err, size_t errlen);
+/* Resident tables for large -k: L2, L3, the bPtable, the giant tables and the lane offsets as khh_tables_new_gpu
+ * builds them (the walk covers only the first m2 baby steps), the level-1 geometry, and the level-1 build's inputs
+ * (64 B per 2^20 baby steps).  No level-1 bloom and no gate exist on the host: khh_session_open builds both on
+ * every device (khb_build_l1_resident) and they stay there.  gate_log2: 0 = sized per device from its free memory
+ * (64 bits per level-1 x, at most 2^38, halved until it fits; none below 4 bits per x), otherwise an explicit size
+ * in [13, 38] for tests and measurements.  On such tables khh_bloom(level 1) and khh_gate return NULL and
+ * khh_tables_save fails; everything else, khh_search included, works. */
+khh_tables* khh_tables_new_resident(const char* n_str, int k, int threads, uint32_t gpl, int device,
+                                    uint32_t gate_log2, double* kernel_ms, char* err, size_t errlen);
+int khh_tables_is_resident(const khh_tables* t);
+/* The gate stages later sessions build on resident tables (khb_set_gate_stage1 / khb_set_gate_stage0 values; the
+ * defaults are KHB_GATE_STAGE1_AUTO and 0). */
+int khh_tables_set_resident_stages(khh_tables* t, uint32_t stage1_log2, uint32_t stage0_log2);
+/* The gate policy of resident builds: log2 bits for l1ext level-1 entries and budget_bytes of device memory. */
+uint32_t khh_resident_gate_log2(uint64_t l1ext, uint64_t budget_bytes);
+/* 1 when a resident build with the AUTO stage-1 setting keeps the fold in front of a gate of 2^gate_log2 bits for
+ * l1ext level-1 entries (at most 32 entries per 64-bit fold block: beyond that the fold passes most x), else 0. */
+int khh_resident_keeps_fold(uint64_t l1ext, uint32_t gate_log2);
 /* Write all four table files into dir. */
 int khh_tables_save(const khh_tables* t, const char* dir, char* err, size_t errlen);
 /* out: [0]=m [1]=m2 [2]=m3 [3]=aux [4]=cycles [5]=N(low64) [6]=l1 extent [7..9]=bloom entries L1..L3 */
@@ -93,6 +112,19 @@ int khh_session_run_ex(khh_session* s, const uint8_t* targets_xy, int n_targets,
                        const uint8_t end_be[32], uint64_t max_chunks, int random_chunks, int* found, uint8_t* keys_be,
                        uint64_t* stats_out, uint32_t stats_len, char* err, size_t errlen);
 void khh_session_close(khh_session* s);
+/* A session on resident tables: what each device built, KHH_RESIDENT_INFO values per device in device order:
+ * [0]=L1 bytes [1]=gate log2 bits (0 = none) [2]=gate probes [3]=stage-1 fold log2 bytes (0 = none)
+ * [4]=stage-0 filter log2 bytes (0 = none) [5]=build kernel microseconds [6]=free and [7]=total device memory
+ * after the build.  Writes up to cap_devices entries; returns the device count (0 on other tables). */
+#define KHH_RESIDENT_INFO 8
+int khh_session_resident_info(const khh_session* s, uint64_t* out, uint32_t cap_devices);
+/* Pass-throughs to the context of the session's device number `index` (any tables): khb_resident_bytes,
+ * khb_resident_read, khb_resident_popcount and khb_gate_probe (include/khbsgs.h, KHB_TABLE_*). */
+int khh_session_resident_bytes(khh_session* s, uint32_t index, int which, uint64_t* bytes);
+int khh_session_resident_read(khh_session* s, uint32_t index, int which, uint64_t offset, uint64_t bytes,
+                              uint8_t* out);
+int khh_session_resident_popcount(khh_session* s, uint32_t index, int which, uint64_t* bits_set);
+int khh_session_gate_probe(khh_session* s, uint32_t index, const uint8_t* xs, uint8_t* out, uint32_t n);
 /* Test hooks: candidate ring capacity per launch (0 = default 2^20; small values drive the
  * split-and-rescan path), the level-0 gate on/off, recording of every level-1 candidate of the next
  * runs (khh_session_recorded), and optionally a replacement level-1 bloom of the tables' geometry

@@ -10,7 +10,7 @@ void words_of_bytes32(uint64_t w[4], const uint8_t x[32]) {
   for (int k = 0; k < 4; ++k) memcpy(&w[k], x + 8 * k, 8);   // little-endian host, XXH_readLE64
 }
 
-int BloomFilter::init2(uint64_t n_entries, long double err) {
+int BloomFilter::init2(uint64_t n_entries, long double err, bool alloc) {
   *this = BloomFilter();
   if (n_entries < 1000 || err <= 0 || err >= 1) return 1;
   entries = n_entries;
@@ -22,7 +22,7 @@ int BloomFilter::init2(uint64_t n_entries, long double err) {
   bits = (uint64_t)allbits;
   bytes = bits / 8 + ((bits % 8) ? 1 : 0);
   hashes = (uint8_t)ceil(0.693147180559945 * bpe);
-  bf.assign(bytes, 0);
+  if (alloc) bf.assign(bytes, 0);
   ready = true;
   return 0;
 }

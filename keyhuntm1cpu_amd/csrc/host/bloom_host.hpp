@@ -18,7 +18,8 @@ struct BloomFilter {
   std::vector<uint8_t> bf;
 
   // bloom_init2: bits = entries * (-ln(err) / ln(2)^2) in long double, hashes = ceil(ln2 * bpe).
-  int init2(uint64_t n_entries, long double err);
+  // alloc = false keeps the geometry only (bf stays empty: the bits live on a device, Tables::resident).
+  int init2(uint64_t n_entries, long double err, bool alloc = true);
   // bloom_check / bloom_add on Get32Bytes(x) (keyhunt.cpp:3945-3946, 4515-4560).
   bool check32(const uint8_t x[32]) const;
   void add32_atomic(const uint8_t x[32]);     // thread-safe byte OR: same bits as mutex + bloom_add

@@ -156,6 +156,10 @@ bool Tables::load_files(const std::string& dir, bool skip_checksum, uint32_t& ha
 
 bool Tables::save_files(const std::string& dir, uint32_t have, std::string& err,
                         const std::function<void(const std::string&)>& log) const {
+  if (resident) {
+    err = "[E] resident tables keep the level-1 bloom on the GPU: there is no table file to write";
+    return false;
+  }
   if (!(have & kFileL1) && !write_blooms(join(dir, file_name(geo, kFileL1)), l1, err, log)) return false;
   if (!(have & kFileL2) && !write_blooms(join(dir, file_name(geo, kFileL2)), l2, err, log)) return false;
   if (!(have & kFileBp)) {

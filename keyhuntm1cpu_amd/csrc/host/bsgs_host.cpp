@@ -122,14 +122,17 @@ bool make_geometry(const char* n_str, int kfactor, Geometry& g, std::string& err
   return true;
 }
 
-// Baby-step walk on the GPU (khb_build_baby): jobs of 2^20 keys, centre key k*2^20 + 513.
-static bool build_baby_gpu(Tables& T, const Geometry& g, const std::vector<Pt>& gn, const Pt& g2n, uint64_t extent,
-                           bool need_l1, bool need_l2, bool need_l3, bool need_bp, uint32_t gate_log2, int device,
-                           int nthreads, double& kernel_ms, std::string& err) {
-  const uint32_t gpj = 1024, gpl = 4;
+// Inputs of the baby-step walk on the GPU (khb_build_baby, khb_build_l1_resident) over `extent` baby steps: jobs
+// of 2^20 keys with centre key k*2^20 + 513, the stride table Gn and the jobs' lane offsets.
+constexpr uint32_t kBuildGpj = 1024, kBuildGpl = 4;
+static void baby_build_inputs(const std::vector<Pt>& gn, const Pt& g2n, uint64_t extent, int nthreads,
+                              std::vector<uint8_t>& centres, std::vector<uint8_t>& tab, std::vector<uint8_t>& offs) {
+  const uint32_t gpj = kBuildGpj, gpl = kBuildGpl;
   const uint64_t job_keys = (uint64_t)gpj * kGrp;
   const uint32_t n_jobs = (uint32_t)((extent + job_keys - 1) / job_keys);
-  std::vector<uint8_t> centres(64 * (size_t)n_jobs), tab(513 * 64), offs(64 * (gpj / gpl));
+  centres.assign(64 * (size_t)n_jobs, 0);
+  tab.assign(513 * 64, 0);
+  offs.assign(64 * (gpj / gpl), 0);
   {
     std::atomic<uint32_t> next{0};
     auto work = [&] {
@@ -144,6 +147,16 @@ static bool build_baby_gpu(Tables& T, const Geometry& g, const std::vector<Pt>& 
   for (int i = 0; i < kHalf; ++i) pt_to_be(tab.data() + 64 * i, gn[i]);
   pt_to_be(tab.data() + 64 * kHalf, g2n);
   for (uint32_t m = 1; m < gpj / gpl; ++m) pt_to_be(offs.data() + 64 * m, mul_g(U256((uint64_t)m * gpl * kGrp)));
+}
+
+// Baby-step walk on the GPU (khb_build_baby).
+static bool build_baby_gpu(Tables& T, const Geometry& g, const std::vector<Pt>& gn, const Pt& g2n, uint64_t extent,
+                           bool need_l1, bool need_l2, bool need_l3, bool need_bp, uint32_t gate_log2, int device,
+                           int nthreads, double& kernel_ms, std::string& err) {
+  const uint32_t gpj = kBuildGpj, gpl = kBuildGpl;
+  std::vector<uint8_t> centres, tab, offs;
+  baby_build_inputs(gn, g2n, extent, nthreads, centres, tab, offs);
+  const uint32_t n_jobs = (uint32_t)(centres.size() / 64);
   khb_ctx* ctx = nullptr;
   int rc = khb_open(device, 0, &ctx);
   if (rc) {
@@ -196,6 +209,21 @@ uint32_t Tables::gate_log2_for(const Geometry& g) {
   return (1ull << lg) < 4 * g.l1ext ? 0 : lg;   // more than ~22 % full: not worth a load
 }
 
+uint32_t Tables::resident_gate_log2(uint64_t l1ext, uint64_t budget_bytes) {
+  if (l1ext == 0) return 0;
+  uint32_t lg = 13;
+  while (lg < 38 && (1ull << lg) < (l1ext << 6)) ++lg;
+  while (lg >= 13 && (1ull << (lg - 3)) > budget_bytes) --lg;
+  return (lg < 13 || (1ull << lg) < 4 * l1ext) ? 0 : lg;
+}
+
+bool Tables::resident_keeps_fold(uint64_t l1ext, uint32_t gate_log2) {
+  if (gate_log2 < 13) return false;
+  const uint64_t gate_bytes = 1ull << (gate_log2 - 3);
+  const uint64_t fold_blocks = (gate_bytes <= (1u << 25) ? 1ull << 21 : 1ull << 25) / 8;   // KHB_GATE_STAGE1_AUTO
+  return l1ext <= 32 * fold_blocks;
+}
+
 void Tables::prepare(const Geometry& g) {
   geo = g;
   l1.assign(256, BloomFilter());
@@ -209,17 +237,22 @@ bool Tables::build(const Geometry& g, int nthreads, uint32_t groups_per_lane, st
   if (!have) prepare(g);
   geo = g;
   for (int i = 0; i < 256; ++i) {
-    if ((!(have & kFileL1) && l1[i].init2(g.items1, kBloomErr)) || (!(have & kFileL2) && l2[i].init2(g.items2, kBloomErr)) ||
+    if ((!(have & kFileL1) && l1[i].init2(g.items1, kBloomErr, !resident)) || (!(have & kFileL2) && l2[i].init2(g.items2, kBloomErr)) ||
         (!(have & kFileL3) && l3[i].init2(g.items3, kBloomErr))) {
       err = "[E] error bloom_init";
       return false;
     }
   }
   if (!(have & kFileBp)) bp.assign(g.m3, XValue());
-  const bool need_l1 = !(have & kFileL1), need_l2 = !(have & kFileL2), need_l3 = !(have & kFileL3),
+  if (resident && (have || gpu_device < 0)) {
+    err = "[E] resident tables are built on a GPU, without table files";
+    return false;
+  }
+  // resident: L1 and its gate are built on each device by Session::open, not here
+  const bool need_l1 = !(have & kFileL1) && !resident, need_l2 = !(have & kFileL2), need_l3 = !(have & kFileL3),
              need_bp = !(have & kFileBp);
   // level-0 gate: built wherever the whole L1 set is walked (the GPU walks it for the gate alone)
-  gate_log2 = (need_l1 || gpu_device >= 0) ? gate_log2_for(g) : 0;
+  gate_log2 = resident ? 0 : (need_l1 || gpu_device >= 0) ? gate_log2_for(g) : 0;
   gate_probes = gate_log2 ? gate_probes_for() : 0;
   gate.assign(gate_log2 ? (size_t)1 << (gate_log2 - 3) : 0, 0);
   // baby steps to walk: all of the L1 extent, or only the first m2 when L1 came from a file
@@ -277,6 +310,11 @@ bool Tables::build(const Geometry& g, int nthreads, uint32_t groups_per_lane, st
                         nthreads, build_gpu_ms, err))
       return false;
     jobs.clear();   // the CPU workers below only compute the lane offsets
+    if (resident) {
+      baby_build_inputs(gn, g2n, g.l1ext, nthreads, build_centres, build_tab, build_offs);
+      build_gpj = kBuildGpj;
+      build_gpl = kBuildGpl;
+    }
     if (progress) progress(extent, extent);
   }
   std::atomic<uint64_t> next_job{0}, next_off{1}, done{0};
@@ -349,6 +387,7 @@ bool Tables::build(const Geometry& g, int nthreads, uint32_t groups_per_lane, st
 }
 
 std::vector<uint8_t> Tables::l1_concat() const {
+  if (resident) return {};
   std::vector<uint8_t> out(256 * l1[0].bytes);
   for (int i = 0; i < 256; ++i) memcpy(out.data() + i * l1[0].bytes, l1[i].bf.data(), l1[0].bytes);
   return out;
@@ -356,6 +395,7 @@ std::vector<uint8_t> Tables::l1_concat() const {
 
 std::vector<uint8_t> Tables::bloom_concat(int level) const {
   const std::vector<BloomFilter>& L = level == 1 ? l1 : level == 2 ? l2 : l3;
+  if (L[0].bf.empty()) return {};        // resident tables: level 1 exists on the devices only
   std::vector<uint8_t> out(256 * L[0].bytes);
   for (int i = 0; i < 256; ++i) memcpy(out.data() + i * L[0].bytes, L[i].bf.data(), L[0].bytes);
   return out;

@@ -59,6 +59,30 @@ struct Tables {
   static uint32_t gate_probes_for();
   std::vector<Pt> lane_offs;             // offs[m] = (m*gpl) * _2GSn
 
+  // Resident tables (large -k): the level-1 bloom and its gate are built on each device by Session::open
+  // (khb_build_l1_resident) and never exist on the host.  l1[] keeps the geometry only (bf empty), `gate` stays
+  // empty and gate_log2 = 0; build() walks only the first m2 baby steps (L2, L3, bPtable) and keeps the level-1
+  // build's inputs instead: the job centres pubkey(k * 2^20 + 513) (64 B per 2^20 baby steps), the stride table
+  // Gn and the build jobs' lane offsets.  Set `resident` (and the options) before build().
+  bool resident = false;
+  uint32_t resident_gate = 0;            // explicit gate size (log2 bits) for tests and measurements; 0 = the policy
+  uint32_t resident_stage1 = 1;          // khb_set_gate_stage1 / khb_set_gate_stage0 for the build (1 = AUTO, 0 = none)
+  uint32_t resident_stage0 = 0;
+  std::vector<uint8_t> build_centres, build_tab, build_offs;
+  uint32_t build_gpj = 0, build_gpl = 0; // groups per build job, groups per lane of build_offs
+  // Gate size (log2 bits, 0 = none) of a resident build: the smallest power of two >= 64 bits per level-1 x, at
+  // most 2^38 (all the 32-bit block index addresses), halved while the gate does not fit budget_bytes (the
+  // device's free memory less L1 and two scratch slots); 0 once that leaves fewer than 4 bits per x.
+  static uint32_t resident_gate_log2(uint64_t l1ext, uint64_t budget_bytes);
+  // Whether a resident build with resident_stage1 = AUTO keeps the library's AUTO stage-1 fold (2 MiB for a gate of
+  // up to 32 MiB, else 32 MiB) in front of a gate of 2^gate_log2 bits: only while the fold holds at most 32 level-1
+  // x per 64-bit block.  With e x per block a probe bit of the fold's lo word is set with 1 - exp(-2e/32), of its
+  // hi word with 1 - exp(-e/32), so a random x passes the fold with (1 - exp(-e/16))^2 (1 - exp(-e/32)): 16 % at
+  // e = 16 (measured 16.8 % at k = 16), 47 % at e = 32, 83 % at e = 64 (measured 83.2 % at k = 64), 99.97 % at
+  // e = 256 (k = 256), where the fold's load is pure cost: 27.8 against 40.0 G giant steps/s without it
+  // (profiles/largek).
+  static bool resident_keeps_fold(uint64_t l1ext, uint32_t gate_log2);
+
   // progress(done, total) is called from the builder threads' coordinator.  `have` marks tables
   // already loaded from -S files (load_files): their baby-step work is skipped, and with L1 loaded
   // only the first m2 baby steps are walked (keyhunt.cpp:1617-1700, "only 3% of the work").

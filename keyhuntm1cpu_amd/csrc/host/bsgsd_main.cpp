@@ -44,6 +44,8 @@ void menu() {
   printf("-g ids      GPU ordinals (default 0)\n");
   printf("--cpu-build build the baby-step tables on the CPU\n");
   printf("--check w   confirm candidates on the host, the gpu, or auto (default host)\n");
+  printf("--resident  large -k: build the level-1 bloom and its gate on every GPU and keep them there (no table\n");
+  printf("            files are read or written; not with --cpu-build)\n");
   exit(EXIT_FAILURE);
 }
 
@@ -122,13 +124,14 @@ int main(int argc, char** argv) {
   signal(SIGPIPE, SIG_IGN);
   printf("[+] Version %s\n", kVersion);
   int kfactor = 1, nthreads = (int)std::thread::hardware_concurrency(), port = 8080;
-  bool skip_checksum = false, cpu_build = false;
+  bool skip_checksum = false, cpu_build = false, resident = false;
   const char* str_n = nullptr;
   std::string ip = "127.0.0.1";
   SearchConfig cfg;
   if (nthreads > 16) nthreads = 16;
   static struct option longopts[] = {{"cpu-build", no_argument, nullptr, 1000},
                                      {"check", required_argument, nullptr, 1001},
+                                     {"resident", no_argument, nullptr, 1002},
                                      {nullptr, 0, nullptr, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "6hk:n:t:p:i:g:", longopts, nullptr)) != -1) {
@@ -173,10 +176,15 @@ int main(int argc, char** argv) {
           exit(EXIT_FAILURE);
         }
         break;
+      case 1002: resident = true; break;
       default:
         fprintf(stderr, "[E] Unknow opcion -%c\n", c);
         exit(0);
     }
+  }
+  if (resident && cpu_build) {
+    fprintf(stderr, "[E] --resident builds the level-1 bloom on the GPU and keeps it there: it cannot be combined with --cpu-build\n");
+    exit(EXIT_FAILURE);
   }
   printf("[+] Mode BSGS secuential\n");
   Geometry geo;
@@ -189,11 +197,11 @@ int main(int argc, char** argv) {
   {
     auto mb = [](uint64_t bytes) { return (float)bytes / 1048576.0f; };
     BloomFilter b;
-    b.init2(geo.items1, 0.000001);
+    b.init2(geo.items1, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m, mb(b.bytes * 256));
-    b.init2(geo.items2, 0.000001);
+    b.init2(geo.items2, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m2, mb(b.bytes * 256));
-    b.init2(geo.items3, 0.000001);
+    b.init2(geo.items3, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m3, mb(b.bytes * 256));
     printf("[+] Allocating %.2f MB for %llu bP Points\n", (double)(geo.m3 * 16 / 1048576), (unsigned long long)geo.m3);
   }
@@ -201,9 +209,10 @@ int main(int argc, char** argv) {
   auto say = [](const std::string& m) { printf("%s", m.c_str()); fflush(stdout); };
   uint32_t have = 0;
   T.prepare(geo);
-  if (!T.load_files(".", skip_checksum, have, err, say) ||
+  T.resident = resident;               // no table files: the level-1 bloom exists on the GPUs only
+  if ((!resident && !T.load_files(".", skip_checksum, have, err, say)) ||
       !T.build(geo, nthreads, 4, err, nullptr, have, cpu_build ? -1 : cfg.devices[0]) ||
-      (have != kFileAll && !T.save_files(".", have, err, say))) {
+      (!resident && have != kFileAll && !T.save_files(".", have, err, say))) {
     fprintf(stderr, "%s\n", err.c_str());
     exit(EXIT_FAILURE);
   }
@@ -213,6 +222,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "[E] %s\n", err.c_str());
     exit(EXIT_FAILURE);
   }
+  print_resident_lines(S);
   const int server_fd = socket(AF_INET, SOCK_STREAM, 0);
   if (server_fd < 0) { perror("socket failed"); exit(EXIT_FAILURE); }
   int opt = 1;

@@ -1,5 +1,6 @@
 #include "engine.hpp"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/random.h>
@@ -520,8 +521,16 @@ int Session::open(const Tables& T, const SearchConfig& cfg, std::string& err) {
   for (int d : cfg.devices) {
     khb_ctx* c = nullptr;
     int rc = khb_open(d, cfg.lanes, &c);
-    if (!rc) rc = khb_load_bloom(c, bf.data(), T.l1[0].bytes, T.l1[0].bits, T.l1[0].hashes);
-    if (!rc && T.gate_log2 && cfg.use_gate) rc = khb_load_gate(c, T.gate.data(), T.gate_log2, T.gate_probes);
+    if (!rc && T.resident) {
+      // each device builds its own level-1 bloom and gate (no peer copies): Gn and the build offsets, the build,
+      // then the search's tables below
+      ResidentInfo info;
+      rc = open_resident(c, info);
+      if (!rc) resident_.push_back(info);
+    } else if (!rc) {
+      rc = khb_load_bloom(c, bf.data(), T.l1[0].bytes, T.l1[0].bits, T.l1[0].hashes);
+      if (!rc && T.gate_log2 && cfg.use_gate) rc = khb_load_gate(c, T.gate.data(), T.gate_log2, T.gate_probes);
+    }
     if (!rc) rc = khb_load_giant_table(c, gsn.data());
     if (!rc) rc = khb_load_lane_offsets(c, offs.data(), (uint32_t)T.lane_offs.size(), T.gpl);
     if (!rc && cfg.cand_cap) rc = khb_set_candidate_capacity(c, cfg.cand_cap);
@@ -537,19 +546,86 @@ int Session::open(const Tables& T, const SearchConfig& cfg, std::string& err) {
   return 0;
 }
 
+// Resident tables on one device: Gn and the build jobs' offsets, then khb_build_l1_resident.  The gate's size is
+// the tables' explicit one or Tables::resident_gate_log2 of what the device has free once L1, the second
+// submission slot (slot 0 is allocated by khb_open) and the check tables a later --check gpu loads are taken out.
+int Session::open_resident(khb_ctx* c, ResidentInfo& info) {
+  const Tables& T = *T_;
+  const BloomFilter& b = T.l1[0];
+  int rc = khb_load_giant_table(c, T.build_tab.data());
+  if (!rc) rc = khb_load_lane_offsets(c, T.build_offs.data(), (uint32_t)(T.build_offs.size() / 64), T.build_gpl);
+  uint64_t free_b = 0, slot_b = 0;
+  if (!rc) rc = khb_mem_info(c, &free_b, nullptr, &slot_b);
+  if (rc) return rc;
+  uint32_t lg = 0;
+  if (cfg_.use_gate) {
+    lg = T.resident_gate;
+    if (!lg) {
+      const uint64_t taken = 256 * b.bytes + slot_b + 256 * (T.l2[0].bytes + T.l3[0].bytes) + 16 * T.bp.size();
+      lg = Tables::resident_gate_log2(T.geo.l1ext, free_b > taken ? free_b - taken : 0);
+    }
+  }
+  const uint32_t probes = lg ? Tables::gate_probes_for() : 0;
+  // the AUTO fold only while it still filters (Tables::resident_keeps_fold); an explicit size is taken as given
+  uint32_t stage1 = T.resident_stage1;
+  if (stage1 == KHB_GATE_STAGE1_AUTO && !Tables::resident_keeps_fold(T.geo.l1ext, lg)) stage1 = 0;
+  rc = khb_set_gate_stage1(c, stage1);
+  if (!rc) rc = khb_set_gate_stage0(c, T.resident_stage0);
+  if (rc) return rc;
+  float ms = 0;
+  rc = khb_build_l1_resident(c, T.build_centres.data(), (uint32_t)(T.build_centres.size() / 64), T.build_gpj,
+                             T.geo.l1ext, b.bytes, b.bits, b.hashes, lg, probes, &ms);
+  if (rc) return rc;
+  info.l1_bytes = 256 * b.bytes;
+  info.gate_log2 = lg;
+  info.gate_probes = probes;
+  info.build_ms = ms;
+  auto log2_of = [&](int which) {
+    uint64_t n = 0;
+    khb_resident_bytes(c, which, &n);
+    uint32_t l = 0;
+    while (n > 1) { n >>= 1; ++l; }
+    return l;
+  };
+  info.fold_log2 = log2_of(KHB_TABLE_FOLD);
+  info.stage0_log2 = log2_of(KHB_TABLE_STAGE0);
+  return khb_mem_info(c, &info.free_bytes, &info.total_bytes, nullptr);
+}
+
 int Session::set_test_hooks(uint32_t cand_cap, bool use_gate, const uint8_t* l1_concat) {
   if (!T_) return KHB_ESTATE;
+  // resident tables: the gate exists on the devices only, so once dropped it cannot be put back
+  if (T_->resident && use_gate && gate_dropped_) return KHB_ESTATE;
   for (void* c : ctx_) {
     khb_ctx* x = (khb_ctx*)c;
     int rc = khb_set_candidate_capacity(x, cand_cap ? cand_cap : (1u << 20));
     if (!rc && l1_concat) rc = khb_load_bloom(x, l1_concat, T_->l1[0].bytes, T_->l1[0].bits, T_->l1[0].hashes);
-    if (!rc) rc = use_gate && T_->gate_log2 ? khb_load_gate(x, T_->gate.data(), T_->gate_log2, T_->gate_probes)
-                                            : khb_load_gate(x, nullptr, 0, 0);
+    if (!rc && T_->resident) {
+      if (!use_gate) rc = khb_load_gate(x, nullptr, 0, 0);
+    } else if (!rc) {
+      rc = use_gate && T_->gate_log2 ? khb_load_gate(x, T_->gate.data(), T_->gate_log2, T_->gate_probes)
+                                     : khb_load_gate(x, nullptr, 0, 0);
+    }
     if (rc) return rc;
   }
+  if (T_->resident && !use_gate) gate_dropped_ = true;
   cfg_.cand_cap = cand_cap;
   cfg_.use_gate = use_gate;
   return 0;
+}
+
+void print_resident_lines(const Session& s) {
+  const std::vector<Session::ResidentInfo>& v = s.resident_info();
+  for (size_t i = 0; i < v.size(); ++i) {
+    const double mb = 1.0 / 1048576.0;
+    char gate[96] = "no gate";
+    if (v[i].gate_log2)
+      snprintf(gate, sizeof gate, "gate 2^%u bits (%.2f MB, %u probes)", v[i].gate_log2,
+               (double)(1ull << (v[i].gate_log2 - 3)) * mb, v[i].gate_probes);
+    printf("[+] GPU %d resident: L1 bloom %.2f MB, %s, build %.1f ms\n", s.config().devices[i],
+           (double)v[i].l1_bytes * mb, gate, v[i].build_ms);
+  }
+  fflush(stdout);
 }
 
 int Session::set_check_mode(int mode) {
@@ -567,6 +643,8 @@ int Session::set_check_mode(int mode) {
 void Session::close() {
   for (void* c : ctx_) khb_close((khb_ctx*)c);
   ctx_.clear();
+  resident_.clear();
+  gate_dropped_ = false;
 }
 
 int Session::run(const std::vector<Target>& targets, const U256& start, const U256& end, const SearchCallbacks& cb,

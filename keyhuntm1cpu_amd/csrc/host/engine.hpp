@@ -127,11 +127,30 @@ class Session {
   // SearchConfig::check_mode for later runs; loads the device check tables when a device mode needs them.
   int set_check_mode(int mode);
 
+  // Resident tables (Tables::resident): what open() built on each device (khb_build_l1_resident), in device order.
+  struct ResidentInfo {
+    uint64_t l1_bytes = 0;
+    uint32_t gate_log2 = 0, gate_probes = 0;     // 0 = no gate
+    uint32_t fold_log2 = 0, stage0_log2 = 0;     // log2 bytes of the stage-1 fold / stage-0 filter, 0 = none
+    double build_ms = 0;                         // the build kernel
+    uint64_t free_bytes = 0, total_bytes = 0;    // device memory after the build
+  };
+  const std::vector<ResidentInfo>& resident_info() const { return resident_; }
+  // Pass-throughs to device `index`'s context (khb_resident_read / khb_resident_popcount / khb_gate_probe).
+  khb_ctx* context(size_t index) const { return index < ctx_.size() ? (khb_ctx*)ctx_[index] : nullptr; }
+
  private:
+  int open_resident(khb_ctx* c, ResidentInfo& info);
   const Tables* T_ = nullptr;
   SearchConfig cfg_;
   std::vector<void*> ctx_;   // khb_ctx*
+  std::vector<ResidentInfo> resident_;
+  bool gate_dropped_ = false;  // resident: set_test_hooks(use_gate = false) freed the gate; only a new open rebuilds it
 };
+
+// --resident: one "[+] GPU <d> resident: L1 ..., gate ..., build ..." line per device of an open session (nothing
+// on other tables).
+void print_resident_lines(const Session& s);
 
 // The check tables of T (level-2/3 blooms, bPtable, AMP2/AMP3, GTable, M constants) into a context.
 int load_check_tables(khb_ctx* c, const Tables& T);

@@ -51,6 +51,8 @@ void menu() {
   printf("-s ns       Number of seconds for the stats output, 0 to omit output.\n");
   printf("-t tn       CPU threads for table build and candidate confirmation\n");
   printf("--cpu-build build the baby-step tables on the CPU (default: on the first GPU)\n");
+  printf("--resident  -m bsgs, large -k: build the level-1 bloom and its gate on every GPU and keep them there\n");
+  printf("            (never in host memory; not with -S or --cpu-build)\n");
   printf("-6          to skip sha256 Checksum on data files\n");
   printf("--gpu       use the GPU path (always on: keyhunt_amd has no CPU giant-step path)\n");
   printf("-g ids      GPU device ids, comma separated (default 0)\n");
@@ -155,7 +157,7 @@ int main(int argc, char** argv) {
   SearchConfig cfg;
   uint32_t gpu_blocks = 0;
   AddressCli ao;
-  bool save_read_file = false, skip_checksum = false, cpu_build = false;
+  bool save_read_file = false, skip_checksum = false, cpu_build = false, resident = false;
   bool endomorphism = false, eth = false;
   const char* kSearch[3] = {"uncompress", "compress", "both"};   // keyhunt.cpp:230
   if (nthreads > 16) nthreads = 16;
@@ -166,6 +168,7 @@ int main(int argc, char** argv) {
                                      {"cpu-build", no_argument, nullptr, 1004},
                                      {"check", required_argument, nullptr, 1005},
                                      {"no-gate", no_argument, nullptr, 1006},
+                                     {"resident", no_argument, nullptr, 1007},
                                      {nullptr, 0, nullptr, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "deh6MqRSB:b:c:C:E:f:I:k:l:m:N:n:p:r:s:t:v:G:8:z:g:", longopts, nullptr)) != -1) {
@@ -270,6 +273,7 @@ int main(int argc, char** argv) {
         }
         break;
       case 1006: cfg.use_gate = false; break;       // the reference's exact level-1 candidate stream
+      case 1007: resident = true; break;            // large -k: level-1 bloom and gate built and kept on each GPU
       case 'z':                                     // keyhunt.cpp:766-772 (used by initBloomFilter, 6559-6576)
         ao.bloom_multiplier = (int)strtol(optarg, nullptr, 10);
         if (ao.bloom_multiplier <= 0) ao.bloom_multiplier = 1;
@@ -340,6 +344,11 @@ int main(int argc, char** argv) {
     exit(EXIT_FAILURE);
   }
   // -e / -I outside the sub-mode "both" are ignored by -m bsgs, as there (keyhunt.cpp:780-789 above)
+  if (resident && (save_read_file || cpu_build)) {
+    fprintf(stderr, "[E] --resident builds the level-1 bloom on the GPU and keeps it there: it cannot be combined with %s\n",
+            save_read_file ? "-S" : "--cpu-build");
+    exit(EXIT_FAILURE);
+  }
   printf("[+] Mode BSGS %s\n", kBsgsModes[bsgs_mode]);
   if (!file) file = "addresses.txt";   // default_fileName, keyhunt.cpp:231
   if (gpu_blocks) cfg.lanes = gpu_blocks * 256u;
@@ -429,17 +438,18 @@ int main(int argc, char** argv) {
   auto mb = [](uint64_t bytes) { return (float)bytes / 1048576.0f; };
   {
     BloomFilter b;
-    b.init2(geo.items1, 0.000001);
+    b.init2(geo.items1, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m, mb(b.bytes * 256));
-    b.init2(geo.items2, 0.000001);
+    b.init2(geo.items2, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m2, mb(b.bytes * 256));
-    b.init2(geo.items3, 0.000001);
+    b.init2(geo.items3, 0.000001, false);
     printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m3, mb(b.bytes * 256));
     printf("[+] Allocating %.2f MB for %llu bP Points\n", (double)(geo.m3 * 16 / 1048576), (unsigned long long)geo.m3);
   }
   // -S: the reference's table files in the working directory (keyhunt.cpp:1373-1613)
   uint32_t have = 0;
   auto say = [](const std::string& m) { printf("%s", m.c_str()); fflush(stdout); };
+  T.resident = resident;
   if (save_read_file) {
     T.prepare(geo);
     if (!T.load_files(".", skip_checksum, have, err, say)) {
@@ -459,7 +469,7 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n", err.c_str());
       exit(EXIT_FAILURE);
     }
-    const uint64_t ext = (have & kFileL1) ? geo.m2 : geo.l1ext;
+    const uint64_t ext = ((have & kFileL1) || resident) ? geo.m2 : geo.l1ext;
     printf("\r[+] processing %llu/%llu bP points : 100%%     \n", (unsigned long long)ext, (unsigned long long)ext);
     if (!(have & kFileBp)) printf("[+] Sorting %llu elements... Done!\n", (unsigned long long)geo.m3);
   } else if (!T.build(geo, nthreads, 4, err, nullptr, have)) {   // giant tables + lane offsets only
@@ -521,7 +531,12 @@ int main(int argc, char** argv) {
       }
     }
   });
-  int rc = run_search(T, targets, n_start, n_end, cfg, cb, found, keys, stats, err);
+  Session session;
+  int rc = session.open(T, cfg, err);
+  if (!rc) {
+    print_resident_lines(session);
+    rc = session.run(targets, n_start, n_end, cb, found, keys, stats, err, cfg.max_chunks, cfg.random_chunks);
+  }
   finished = true;
   stat_thread.join();
   if (rc) { fprintf(stderr, "%s\n", err.c_str()); exit(EXIT_FAILURE); }

@@ -85,6 +85,47 @@ khh_tables* khh_tables_new_gpu(const char* n_str, int k, int threads, uint32_t g
   return t;
 }
 
+khh_tables* khh_tables_new_resident(const char* n_str, int k, int threads, uint32_t gpl, int device,
+                                    uint32_t gate_log2, double* kernel_ms, char* err, size_t errlen) {
+  Geometry g;
+  std::string e;
+  if (!make_geometry(n_str, k, g, e)) { set_err(err, errlen, e); return nullptr; }
+  if (gate_log2 && (gate_log2 < 13 || gate_log2 > 38)) {
+    set_err(err, errlen, "[E] resident gate size: 0 or 13..38 (log2 bits)");
+    return nullptr;
+  }
+  khh_tables* t = new khh_tables();
+  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+  t->t.resident = true;
+  t->t.resident_gate = gate_log2;
+  if (!t->t.build(g, threads, gpl ? gpl : 4, e, nullptr, 0, device)) {
+    set_err(err, errlen, e);
+    delete t;
+    return nullptr;
+  }
+  if (kernel_ms) *kernel_ms = t->t.build_gpu_ms;
+  return t;
+}
+
+int khh_tables_is_resident(const khh_tables* t) { return t && t->t.resident ? 1 : 0; }
+
+int khh_tables_set_resident_stages(khh_tables* t, uint32_t stage1_log2, uint32_t stage0_log2) {
+  if (!t || !t->t.resident) return KHB_EINVAL;
+  if (stage1_log2 > 1 && (stage1_log2 < 10 || stage1_log2 > 31)) return KHB_EINVAL;
+  if (stage0_log2 > 1 && (stage0_log2 < 10 || stage0_log2 > 30)) return KHB_EINVAL;
+  t->t.resident_stage1 = stage1_log2;
+  t->t.resident_stage0 = stage0_log2;
+  return 0;
+}
+
+uint32_t khh_resident_gate_log2(uint64_t l1ext, uint64_t budget_bytes) {
+  return Tables::resident_gate_log2(l1ext, budget_bytes);
+}
+
+int khh_resident_keeps_fold(uint64_t l1ext, uint32_t gate_log2) {
+  return Tables::resident_keeps_fold(l1ext, gate_log2) ? 1 : 0;
+}
+
 int khh_tables_save(const khh_tables* t, const char* dir, char* err, size_t errlen) {
   std::string e;
   if (!t->t.save_files(dir ? dir : ".", 0, e, nullptr)) {
@@ -108,6 +149,7 @@ const uint8_t* khh_bloom(const khh_tables* t, int level, int idx, uint64_t* byte
   if (bytes) *bytes = b.bytes;
   if (bits) *bits = b.bits;
   if (hashes) *hashes = b.hashes;
+  if (level == 1 && t->t.resident) return nullptr;   // the geometry only: the bits live on the devices
   return b.bf.data();
 }
 
@@ -201,6 +243,39 @@ khh_session* khh_session_open(const khh_tables* t, const int* devices, int n_dev
 }
 
 void khh_session_close(khh_session* s) { delete s; }
+
+int khh_session_resident_info(const khh_session* s, uint64_t* out, uint32_t cap_devices) {
+  if (!s) return KHB_EINVAL;
+  const std::vector<Session::ResidentInfo>& v = s->s.resident_info();
+  for (size_t i = 0; out && i < v.size() && i < cap_devices; ++i) {
+    const uint64_t r[KHH_RESIDENT_INFO] = {v[i].l1_bytes, v[i].gate_log2, v[i].gate_probes, v[i].fold_log2,
+                                           v[i].stage0_log2, (uint64_t)(v[i].build_ms * 1e3), v[i].free_bytes,
+                                           v[i].total_bytes};
+    memcpy(out + KHH_RESIDENT_INFO * i, r, sizeof r);
+  }
+  return (int)v.size();
+}
+
+int khh_session_resident_bytes(khh_session* s, uint32_t index, int which, uint64_t* bytes) {
+  khb_ctx* c = s ? s->s.context(index) : nullptr;
+  return c ? khb_resident_bytes(c, which, bytes) : KHB_EINVAL;
+}
+
+int khh_session_resident_read(khh_session* s, uint32_t index, int which, uint64_t offset, uint64_t bytes,
+                              uint8_t* out) {
+  khb_ctx* c = s ? s->s.context(index) : nullptr;
+  return c ? khb_resident_read(c, which, offset, bytes, out) : KHB_EINVAL;
+}
+
+int khh_session_resident_popcount(khh_session* s, uint32_t index, int which, uint64_t* bits_set) {
+  khb_ctx* c = s ? s->s.context(index) : nullptr;
+  return c ? khb_resident_popcount(c, which, bits_set) : KHB_EINVAL;
+}
+
+int khh_session_gate_probe(khh_session* s, uint32_t index, const uint8_t* xs, uint8_t* out, uint32_t n) {
+  khb_ctx* c = s ? s->s.context(index) : nullptr;
+  return c ? khb_gate_probe(c, xs, out, n) : KHB_EINVAL;
+}
 
 int khh_session_run(khh_session* s, const uint8_t* targets_xy, int n_targets, const uint8_t start_be[32],
                     const uint8_t end_be[32], uint64_t max_chunks, int random_chunks, int* found, uint8_t* keys_be,

@@ -99,6 +99,65 @@ __global__ void k_probe(const uint8_t* __restrict__ bloom, BloomGeom g, const Fe
   hit[i] = bloom_probe_x(bloom, g, xs[i]) ? 1 : 0;
 }
 
+// ---- gate stages built on the device from a resident gate (khb_build_l1_resident); the bits are those of
+// khb_load_gate's host loops.
+// One probe: every block's hi word set, so the kernels' fixed three-probe test gives the one-probe answer.
+__global__ void k_gate_hifill(uint2* __restrict__ gate, uint64_t nb) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nb; j += stride) gate[j].y = 0xFFFFFFFFu;
+}
+
+// Stage-1 fold: thread i owns fold block i = OR of the gate's blocks i, i + nb1, ... (coalesced, no atomics).
+__global__ void k_gate_fold(const uint2* __restrict__ gate, uint64_t nb, uint2* __restrict__ fold, uint32_t nb1) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb1) return;
+  uint2 f = make_uint2(0u, 0u);
+  for (uint64_t j = i; j < nb; j += nb1) {
+    const uint2 g = gate[j];
+    f.x |= g.x;
+    f.y |= g.y;
+  }
+  fold[i] = f;
+}
+
+// Stage-0 filter: word i = OR of the hi words of the gate's blocks j with j mod nw0 == i.  nw0 divides the fold's
+// block count, so those are the hi words of the fold's blocks i, i + nw0, ...
+__global__ void k_gate_stage0(const uint2* __restrict__ fold, uint32_t nb1, uint32_t* __restrict__ z, uint32_t nw0) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nw0) return;
+  uint32_t v = 0;
+  for (uint32_t j = i; j < nb1; j += nw0) v |= fold[j].y;
+  z[i] = v;
+}
+
+// Bits set in n_words 32-bit words (grid-stride; one atomic per block).
+__global__ void k_popcount(const uint32_t* __restrict__ w, uint64_t n_words, unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long part[256 / 64];
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  unsigned long long n = 0;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_words; j += stride) n += __popc(w[j]);
+  for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (uint32_t k = 1; k < blockDim.x / 64; ++k) n += part[k];
+    atomicAdd(total, n);
+  }
+}
+
+// Gate self-test with the scan's own device functions: bit 0 = the full gate passes x, bit 1 = the stage-1 fold
+// (1 when there is none), bit 2 = the stage-0 filter (1 when there is none).
+__global__ void k_gate_probe(ScanArgs A, const Fe* __restrict__ xs, uint8_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fe x = xs[i];
+  const GateBits b = gate_bits(x.v[1], gate_s2(A));
+  uint32_t r = gate_block_pass(gate_block(A.gate, A.gate_mask, x), b) ? 1u : 0u;
+  r |= (!A.gate1 || gate_block_pass(gate_block(A.gate1, A.gate1_mask, x), b)) ? 2u : 0u;
+  r |= (!A.gate0 || (int32_t)shl_mod32(A.gate0[x.v[0] & A.gate0_mask], b.a1) < 0) ? 4u : 0u;
+  out[i] = (uint8_t)r;
+}
+
 }  // namespace
 
 // One submission's device state.  A context owns two (KHB_QUEUE_DEPTH): khb_submit fills the next
@@ -134,8 +193,9 @@ struct khb_ctx {
   int last_hip = 0;
   uint32_t handoff_seen = 0, handoff_total = 0;   // the last collect's epilogue wave count (khb_last_handoff)
   uint32_t lanes = 0;
-  uint8_t* d_bloom = nullptr;
+  uint8_t* d_bloom = nullptr;          // 256 x geom.bytes_per_sub bytes (a whole number of 32-bit words)
   BloomGeom geom{};
+  uint64_t gate_bytes = 0;             // of d_gate (up to 32 GiB: khb_build_l1_resident)
   uint8_t* d_gate = nullptr;           // level-0 gate (khb_load_gate), null = none
   uint8_t* d_gate1 = nullptr;          // its stage-1 fold, null = none
   uint32_t gate1_mask = 0;
@@ -428,6 +488,60 @@ int ensure_gofs(khb_ctx* c) {
   return KHB_OK;
 }
 
+// The sizes (log2 bytes, 0 = none) of the stage-1 fold of a gate of `bytes` bytes and of the stage-0 filter in front
+// of a fold of 2^f_log2 bytes, as set by khb_set_gate_stage1 / khb_set_gate_stage0 (khb_load_gate has the
+// measurements behind the AUTO rules).
+uint32_t fold_log2_for(const khb_ctx* c, uint64_t bytes) {
+  return c->gate1_log2 != KHB_GATE_STAGE1_AUTO ? c->gate1_log2 : bytes <= (1u << 25) ? 21u : 25u;
+}
+uint32_t stage0_log2_for(const khb_ctx* c, uint32_t f_log2) {
+  return c->gate0_log2 != KHB_GATE_STAGE0_AUTO ? c->gate0_log2 : f_log2 > 21 ? 21u : 0u;
+}
+
+// khb_load_gate's derived structures for a gate already on the device (c->d_gate, gate_bytes, gate_probes set):
+// the one-probe hi-word fill, the stage-1 fold and the stage-0 filter, by the same rules, with device kernels.
+int build_gate_stages_device(khb_ctx* c, hipStream_t stream) {
+  const uint64_t bytes = c->gate_bytes, nb = bytes / 8;
+  const uint32_t fill_blocks = (uint32_t)(nb / 256 < 65536 ? (nb + 255) / 256 : 65536);
+  if (c->gate_probes == 1) {
+    hipLaunchKernelGGL(k_gate_hifill, dim3(fill_blocks), dim3(256), 0, stream, (uint2*)c->d_gate, nb);
+    KHB_TRY(c, hipGetLastError());
+  }
+  const uint32_t f_log2 = fold_log2_for(c, bytes);
+  if (f_log2 && (1ull << f_log2) < bytes) {
+    const uint32_t nb1 = (uint32_t)((1ull << f_log2) / 8);
+    KHB_TRY(c, hipMalloc(&c->d_gate1, (size_t)nb1 * 8));
+    hipLaunchKernelGGL(k_gate_fold, dim3((nb1 + 255) / 256), dim3(256), 0, stream, (const uint2*)c->d_gate, nb,
+                       (uint2*)c->d_gate1, nb1);
+    KHB_TRY(c, hipGetLastError());
+    c->gate1_mask = nb1 - 1;
+    const uint32_t z_log2 = stage0_log2_for(c, f_log2);
+    if (z_log2 && c->gate_probes >= 2 && (1ull << z_log2) < (uint64_t)nb1 * 8) {
+      const uint32_t nw0 = (uint32_t)((1ull << z_log2) / 4);
+      KHB_TRY(c, hipMalloc(&c->d_gate0, (size_t)nw0 * 4));
+      hipLaunchKernelGGL(k_gate_stage0, dim3((nw0 + 255) / 256), dim3(256), 0, stream, (const uint2*)c->d_gate1, nb1,
+                         c->d_gate0, nw0);
+      KHB_TRY(c, hipGetLastError());
+      c->gate0_mask = nw0 - 1;
+    }
+  }
+  KHB_TRY(c, hipStreamSynchronize(stream));
+  return KHB_OK;
+}
+
+// An installed table (khb_resident_read / khb_resident_popcount): its device address and size in bytes.
+bool resident_table(const khb_ctx* c, int which, const uint8_t*& p, uint64_t& bytes) {
+  switch (which) {
+    case KHB_TABLE_L1: p = c->d_bloom; bytes = 256 * c->geom.bytes_per_sub; break;
+    case KHB_TABLE_GATE: p = c->d_gate; bytes = c->gate_bytes; break;
+    case KHB_TABLE_FOLD: p = c->d_gate1; bytes = ((uint64_t)c->gate1_mask + 1) * 8; break;
+    case KHB_TABLE_STAGE0: p = (const uint8_t*)c->d_gate0; bytes = ((uint64_t)c->gate0_mask + 1) * 4; break;
+    default: p = nullptr; bytes = 0; break;
+  }
+  if (!p) bytes = 0;
+  return p != nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -589,8 +703,10 @@ int khb_load_gate(khb_ctx* c, const uint8_t* gate, uint32_t log2_bits, uint32_t 
   if (c->d_gate1) { hipFree(c->d_gate1); c->d_gate1 = nullptr; }
   if (c->d_gate0) { hipFree(c->d_gate0); c->d_gate0 = nullptr; }
   c->gate_mask = c->gate1_mask = c->gate0_mask = 0;
+  c->gate_bytes = 0;
   if (!gate) return KHB_OK;
   const size_t bytes = (size_t)1 << (log2_bits - 3);
+  c->gate_bytes = bytes;
   // one probe: every block's hi word set on the device copy, so the kernels' fixed three-probe test
   // (scan_kernels.hpp gate_block_pass: probe 1 reads hi, probe 2 repeats probe 0) gives the one-probe answer
   std::vector<uint64_t> one;
@@ -609,7 +725,7 @@ int khb_load_gate(khb_ctx* c, const uint8_t* gate, uint32_t log2_bits, uint32_t 
   // 32 MiB fold of a larger one (k = 4: the 128 MiB gate beside the 57.5 MiB L1 bloom).  Round 4 (full prefix stream)
   // had measured 16 MiB 3.5 % faster than 32 MiB (profiles/r04l/k4_stage1_ab.txt); with the half prefix stream's
   // halved MALL traffic 32 MiB is 1.3 % faster than 16 MiB and 0.8 % than 64 MiB (5 rounds each, profiles/r06e).
-  const uint32_t f_log2 = c->gate1_log2 != KHB_GATE_STAGE1_AUTO ? c->gate1_log2 : bytes <= (1u << 25) ? 21u : 25u;
+  const uint32_t f_log2 = fold_log2_for(c, bytes);
   if (f_log2 && (size_t)1 << f_log2 < bytes) {
     // stage 1: the gate OR-folded to 2^f_log2 bytes (a superset: no member is ever dropped)
     const size_t nb1 = ((size_t)1 << f_log2) / 8, nb = bytes / 8;
@@ -623,7 +739,7 @@ int khb_load_gate(khb_ctx* c, const uint8_t* gate, uint32_t log2_bits, uint32_t 
     // fold larger than 2 MiB (k >= 4, where the fold is read from the MALL for every x); none at k = 1, whose
     // 2 MiB fold is itself L2-resident.  With one probe every hi word is set (above), so the filter would pass
     // everything: none.
-    const uint32_t z_log2 = c->gate0_log2 != KHB_GATE_STAGE0_AUTO ? c->gate0_log2 : f_log2 > 21 ? 21u : 0u;
+    const uint32_t z_log2 = stage0_log2_for(c, f_log2);
     if (z_log2 && probes >= 2 && (size_t)1 << z_log2 < nb1 * 8) {
       // stage 0: the hi words of the gate's blocks (probe 1's bit of every member) OR-folded to 2^z_log2 bytes
       const size_t nw0 = ((size_t)1 << z_log2) / 4;
@@ -1184,7 +1300,7 @@ int khb_build_baby(khb_ctx* c, const uint8_t* centres, uint32_t n_jobs, uint32_t
     e = hipMalloc(&dw[l], 256 * words * 4);
     if (e == hipSuccess) e = hipMemsetAsync(dw[l], 0, 256 * words * 4, S.stream);
     A.bw[l] = dw[l];
-    A.bwords[l] = words;
+    A.bstride[l] = words * 32;           // word-aligned sub-blooms, repacked below
     A.bgeom[l] = bloom_geom(bytes_per_sub[l], bits_per_sub[l], hashes[l]);
   }
   if (e == hipSuccess && bp && m3) {
@@ -1212,7 +1328,7 @@ int khb_build_baby(khb_ctx* c, const uint8_t* centres, uint32_t n_jobs, uint32_t
   }
   for (int l = 0; l < 3 && e == hipSuccess; ++l) {
     if (!outs[l]) continue;
-    const uint64_t words = A.bwords[l], nb = bytes_per_sub[l];
+    const uint64_t words = A.bstride[l] / 32, nb = bytes_per_sub[l];
     uint8_t* tmp = (uint8_t*)malloc(256 * words * 4);
     if (!tmp) { e = hipErrorOutOfMemory; break; }
     e = hipMemcpy(tmp, dw[l], 256 * words * 4, hipMemcpyDeviceToHost);
@@ -1227,6 +1343,191 @@ int khb_build_baby(khb_ctx* c, const uint8_t* centres, uint32_t n_jobs, uint32_t
   hipFree(dgate);
   if (e != hipSuccess) return hip_fail(c, e);
   return walked == (uint64_t)n_jobs * groups_per_job ? KHB_OK : KHB_EINCOMPLETE;
+}
+
+// ------------------------------------------------------------- resident level-1 bloom and gate
+int khb_build_l1_resident(khb_ctx* c, const uint8_t* centres, uint32_t n_jobs, uint32_t groups_per_job,
+                          uint64_t l1ext, uint64_t bytes_per_sub, uint64_t bits_per_sub, uint32_t hashes,
+                          uint32_t gate_log2, uint32_t gate_probes, float* kernel_ms) {
+  int rc = check_scan_args(c, centres, n_jobs, 0, groups_per_job, false);
+  if (rc) return rc;
+  if (l1ext == 0 || bits_per_sub < 2 || (bits_per_sub + 7) / 8 != bytes_per_sub || hashes == 0 || hashes > 255)
+    return KHB_EINVAL;
+  if (gate_log2 && (gate_log2 < 13 || gate_log2 > 38 || gate_probes < 1 || gate_probes > KHB_GATE_MAX_PROBES))
+    return KHB_EINVAL;
+  if (c->queued) return KHB_EBUSY;
+  KHB_TRY(c, hipSetDevice(c->device));
+  Slot& S = c->slot[0];
+  if ((rc = ensure_centres(c, S, n_jobs))) return rc;
+  pts_from_be(S.h_centres, centres, n_jobs);
+  // a build replaces whatever is installed
+  hipFree(c->d_bloom);
+  hipFree(c->d_gate);
+  hipFree(c->d_gate1);
+  hipFree(c->d_gate0);
+  c->d_bloom = c->d_gate = c->d_gate1 = nullptr;
+  c->d_gate0 = nullptr;
+  c->gate_mask = c->gate1_mask = c->gate0_mask = 0;
+  c->gate_bytes = 0;
+  c->gate_probes = 0;
+  c->geom = BloomGeom{};
+  const uint64_t l1_bytes = 256 * bytes_per_sub, gate_bytes = gate_log2 ? 1ull << (gate_log2 - 3) : 0;
+  auto drop = [&](hipError_t e) {        // nothing half-built stays installed
+    hipFree(c->d_bloom);
+    hipFree(c->d_gate);
+    hipFree(c->d_gate1);
+    hipFree(c->d_gate0);
+    c->d_bloom = c->d_gate = c->d_gate1 = nullptr;
+    c->d_gate0 = nullptr;
+    c->gate_mask = c->gate1_mask = c->gate0_mask = 0;
+    c->gate_bytes = 0;
+    c->geom = BloomGeom{};
+    return e == hipSuccess ? KHB_OK : hip_fail(c, e);
+  };
+  hipError_t e = hipMalloc(&c->d_bloom, l1_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(c->d_bloom, 0, l1_bytes, S.stream);
+  if (e == hipSuccess && gate_bytes) {
+    e = hipMalloc(&c->d_gate, gate_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_gate, 0, gate_bytes, S.stream);
+  }
+  if (e != hipSuccess) return drop(e);
+  ScanArgs A = make_args(c, S, n_jobs, 0, groups_per_job);
+  A.bloom = nullptr;                     // the walk only writes
+  A.gate = nullptr;
+  A.job_keys = (uint64_t)groups_per_job * KHB_GROUP;
+  A.blimit[0] = l1ext;
+  A.bw[0] = reinterpret_cast<uint32_t*>(c->d_bloom);
+  A.bstride[0] = bytes_per_sub * 8;      // packed: the layout the probe reads, no repack
+  A.bgeom[0] = bloom_geom(bytes_per_sub, bits_per_sub, hashes);
+  if (gate_bytes) {
+    A.gate_w = reinterpret_cast<uint32_t*>(c->d_gate);
+    A.glimit = l1ext;
+    A.gate_mask = (uint32_t)((1ull << (gate_log2 - 6)) - 1);
+    A.gate_probes = gate_probes;
+  }
+  e = hipMemcpyAsync(S.d_centres, S.h_centres, sizeof(AffPt) * n_jobs, hipMemcpyHostToDevice, S.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S.d_counters, 0, kCounterBytes, S.stream);
+  S.counters_zero = false;
+  if (e == hipSuccess) e = hipEventRecord(S.ev0, S.stream);
+  if (e == hipSuccess) {
+    launch_baby(c->lanes / kBlock, S.stream, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(S.ev1, S.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(S.stream);
+  if (e == hipSuccess) e = hipMemcpy(S.h_counters, S.d_counters, kCounterBytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return drop(e);
+  if (walked_groups(S) != (uint64_t)n_jobs * groups_per_job) {
+    drop(hipSuccess);
+    return KHB_EINCOMPLETE;
+  }
+  if (kernel_ms) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, S.ev0, S.ev1) != hipSuccess) ms = -1.f;
+    *kernel_ms = ms;
+  }
+  c->geom = A.bgeom[0];
+  if (gate_bytes) {
+    c->gate_bytes = gate_bytes;
+    c->gate_mask = A.gate_mask;
+    c->gate_probes = gate_probes;
+    if ((rc = build_gate_stages_device(c, S.stream))) {
+      drop(hipSuccess);
+      return rc;
+    }
+  }
+  return KHB_OK;
+}
+
+int khb_mem_info(khb_ctx* c, uint64_t* free_bytes, uint64_t* total_bytes, uint64_t* slot_bytes) {
+  if (!c) return KHB_EINVAL;
+  KHB_TRY(c, hipSetDevice(c->device));
+  size_t f = 0, t = 0;
+  KHB_TRY(c, hipMemGetInfo(&f, &t));
+  if (free_bytes) *free_bytes = f;
+  if (total_bytes) *total_bytes = t;
+  if (slot_bytes) *slot_bytes = sizeof(Fe) * kScratchEntries * c->lanes;
+  return KHB_OK;
+}
+
+int khb_resident_bytes(const khb_ctx* c, int which, uint64_t* bytes) {
+  if (!c || !bytes || which < KHB_TABLE_L1 || which > KHB_TABLE_STAGE0) return KHB_EINVAL;
+  const uint8_t* p;
+  resident_table(c, which, p, *bytes);
+  return KHB_OK;
+}
+
+int khb_resident_read(khb_ctx* c, int which, uint64_t offset, uint64_t bytes, uint8_t* out) {
+  if (!c || which < KHB_TABLE_L1 || which > KHB_TABLE_STAGE0 || (bytes && !out)) return KHB_EINVAL;
+  const uint8_t* p;
+  uint64_t size;
+  if (!resident_table(c, which, p, size)) return KHB_ESTATE;
+  if (offset > size || bytes > size - offset) return KHB_EINVAL;
+  if (c->queued) return KHB_EBUSY;
+  KHB_TRY(c, hipSetDevice(c->device));
+  if (bytes) KHB_TRY(c, hipMemcpy(out, p + offset, bytes, hipMemcpyDeviceToHost));
+  return KHB_OK;
+}
+
+int khb_resident_popcount(khb_ctx* c, int which, uint64_t* bits_set) {
+  if (!c || !bits_set || which < KHB_TABLE_L1 || which > KHB_TABLE_STAGE0) return KHB_EINVAL;
+  const uint8_t* p;
+  uint64_t size;
+  if (!resident_table(c, which, p, size)) return KHB_ESTATE;
+  if (c->queued) return KHB_EBUSY;
+  KHB_TRY(c, hipSetDevice(c->device));
+  Slot& S = c->slot[0];
+  unsigned long long* d = nullptr;
+  KHB_TRY(c, hipMalloc(&d, sizeof *d));
+  unsigned long long v = 0;
+  hipError_t e = hipMemsetAsync(d, 0, sizeof *d, S.stream);
+  if (e == hipSuccess) {
+    const uint64_t words = size / 4;     // every table is a whole number of 32-bit words
+    const uint32_t blocks = (uint32_t)(words / 256 < 16384 ? (words + 255) / 256 : 16384);
+    hipLaunchKernelGGL(k_popcount, dim3(blocks), dim3(256), 0, S.stream, (const uint32_t*)p, words, d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(S.stream);
+  if (e == hipSuccess) e = hipMemcpy(&v, d, sizeof v, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) return hip_fail(c, e);
+  *bits_set = v;
+  return KHB_OK;
+}
+
+int khb_gate_probe(khb_ctx* c, const uint8_t* xs, uint8_t* out, uint32_t n) {
+  if (!c || !xs || !out || n == 0) return KHB_EINVAL;
+  if (!c->d_gate) return KHB_ESTATE;
+  if (c->queued) return KHB_EBUSY;
+  KHB_TRY(c, hipSetDevice(c->device));
+  Slot& S = c->slot[0];
+  Fe* h = (Fe*)malloc(sizeof(Fe) * n);
+  if (!h) return KHB_ENOMEM;
+  for (uint32_t i = 0; i < n; ++i) fe_from_be(h[i], xs + 32 * (size_t)i);
+  Fe* d = nullptr;
+  uint8_t* dout = nullptr;
+  hipError_t e = hipMalloc(&d, sizeof(Fe) * n);
+  if (e == hipSuccess) e = hipMalloc(&dout, n);
+  if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(Fe) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    ScanArgs A{};
+    A.gate = c->d_gate;
+    A.gate_mask = c->gate_mask;
+    A.gate_probes = c->gate_probes;
+    A.gate1 = c->d_gate1;
+    A.gate1_mask = c->gate1_mask;
+    A.gate0 = c->d_gate0;
+    A.gate0_mask = c->gate0_mask;
+    hipLaunchKernelGGL(k_gate_probe, dim3((n + 255) / 256), dim3(256), 0, S.stream, A, (const Fe*)d, dout, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(S.stream);
+  if (e == hipSuccess) e = hipMemcpy(out, dout, n, hipMemcpyDeviceToHost);
+  hipFree(d);
+  hipFree(dout);
+  free(h);
+  if (e != hipSuccess) return hip_fail(c, e);
+  return KHB_OK;
 }
 
 }  // extern "C"

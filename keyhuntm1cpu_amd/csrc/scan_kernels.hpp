@@ -144,10 +144,13 @@ struct ScanArgs {
   uint8_t* __restrict__ xdump;         // dump modes only
   uint32_t* __restrict__ ahits;        // -m address hits: {job, group, t, kind} x ahit_cap
   uint32_t ahit_cap;
-  // kBaby: word-aligned blooms (sub-bloom stride bwords[l] 32-bit words; null = level skipped)
+  // kBaby: blooms written as 32-bit words (null = level skipped).  Bit pos of sub-bloom sub is bit
+  // sub * bstride[l] + pos of the level: bstride = 32 x words per sub-bloom for khb_build_baby's word-aligned
+  // sub-blooms, 8 x bytes_per_sub for the packed layout the probe reads (khb_build_l1_resident), where a word
+  // may straddle two sub-blooms
   uint32_t* __restrict__ bw[3];
   BloomGeom bgeom[3];
-  uint64_t bwords[3];
+  uint64_t bstride[3];
   uint64_t blimit[3];                  // ic < blimit[l] goes into level l (l1ext, m2, m3)
   uint32_t* __restrict__ bp;           // m3 x 16-byte struct bsgs_xvalue records (null = skipped)
   // level-0 gate (khb_load_gate): a blocked bloom of (gate_mask + 1) 64-bit blocks; x selects
@@ -471,9 +474,10 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
   }
 }
 
-// bloom_add (bloom.cpp:61-85, 159-162) of a 32-byte x into sub-bloom x[0] of a word-aligned level.
-__device__ __forceinline__ void bloom_add_words(uint32_t* __restrict__ words, const BloomGeom& g, uint64_t a,
-                                                uint64_t b) {
+// bloom_add (bloom.cpp:61-85, 159-162) of a 32-byte x into the sub-bloom of a level that starts at bit `base`
+// (ScanArgs::bstride) of `words`.
+__device__ __forceinline__ void bloom_add_words(uint32_t* __restrict__ words, uint64_t base, const BloomGeom& g,
+                                                uint64_t a, uint64_t b) {
   uint64_t pos = mod_bits(a, g);
   const uint64_t bm = mod_bits(b, g);
   uint64_t h = a;
@@ -486,8 +490,9 @@ __device__ __forceinline__ void bloom_add_words(uint32_t* __restrict__ words, co
       if (pos >= g.bits) pos -= g.bits;
       if (wrapped) pos = (pos >= g.wrap) ? pos - g.wrap : pos + g.bits - g.wrap;
     }
-    // bf[pos >> 3] |= 1 << (pos & 7): little-endian words, so bit (pos & 31) of word pos >> 5
-    atomicOr(words + (pos >> 5), 1u << (pos & 31));
+    // bf[pos >> 3] |= 1 << (pos & 7): little-endian words, so bit (bit & 31) of the aligned word bit >> 5
+    const uint64_t bit = base + pos;
+    atomicOr(words + (bit >> 5), 1u << (bit & 31));
   }
 }
 
@@ -499,15 +504,16 @@ __device__ __forceinline__ void baby_point(const ScanArgs& A, const Fe& x, uint3
   x_words(w, x);
   const uint64_t a = xxh64_32(w, KHB_BLOOM_SEED);
   if (A.gate_w && ic < A.glimit) {
-    const uint32_t blk = x.v[0] & A.gate_mask;
+    // the word index in 64 bits: a 2^38-bit gate has 2^32 blocks, 2^33 words
+    const uint64_t w0 = 2 * (uint64_t)(x.v[0] & A.gate_mask);
     for (uint32_t p = 0; p < A.gate_probes; ++p)      // gate_block_pass: bit (w1 >> 5p) mod 32 of word p mod 2
-      atomicOr(A.gate_w + 2 * blk + (p & 1u), 1u << ((x.v[1] >> (5 * p)) & 31u));
+      atomicOr(A.gate_w + (w0 + (p & 1u)), 1u << ((x.v[1] >> (5 * p)) & 31u));
   }
   const uint64_t b = xxh64_32(w, a);
   const uint32_t sub = x.v[7] >> 24;
 #pragma unroll 1
   for (int l = 0; l < 3; ++l)
-    if (A.bw[l] && ic < A.blimit[l]) bloom_add_words(A.bw[l] + sub * A.bwords[l], A.bgeom[l], a, b);
+    if (A.bw[l] && ic < A.blimit[l]) bloom_add_words(A.bw[l], sub * A.bstride[l], A.bgeom[l], a, b);
   if (A.bp && ic < A.blimit[2]) {
     // struct bsgs_xvalue {value = x bytes 16..21 (Get32Bytes order), pad[2] = 0, index = ic}
     uint32_t* o = A.bp + 4 * ic;

@@ -59,6 +59,7 @@ class Stats(C.Structure):
 
 _libs: dict[str, C.CDLL] = {}
 KHB_ABI_VERSION = 7
+TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
 
 
 def lib(path: str | None = None) -> C.CDLL:
@@ -109,6 +110,14 @@ def lib(path: str | None = None) -> C.CDLL:
             L.khb_set_gate_stage0.argtypes = [C.c_void_p, C.c_uint32]
             L.khb_gate_stages.argtypes = [C.c_void_p]
             L.khb_last_handoff.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]
+        if hasattr(L, "khb_build_l1_resident"):  # the resident additions to ABI 7
+            L.khb_build_l1_resident.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_float)]
+            L.khb_mem_info.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]
+            L.khb_resident_bytes.argtypes = [C.c_void_p, C.c_int, P(C.c_uint64)]
+            L.khb_resident_read.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
+            L.khb_resident_popcount.argtypes = [C.c_void_p, C.c_int, P(C.c_uint64)]
+            L.khb_gate_probe.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
         L.khb_load_lane_offsets.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32]
         L.khb_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]
         L.khb_collect.argtypes = [C.c_void_p, P(Cand), C.c_uint32, P(Degenerate), C.c_uint32, P(Stats)]
@@ -281,6 +290,47 @@ class Engine:
         n = len(xs) // 32
         out = C.create_string_buffer(n)
         _check(self.L.khb_probe(self.h, xs, out, n), self.h, self.L)
+        return out.raw
+
+    # ---- resident level-1 bloom and gate (additions to ABI 7) ----
+    def build_l1_resident(self, centres: bytes, groups_per_job: int, l1ext: int, bytes_per_sub: int, bits: int,
+                          hashes: int, gate_log2: int = 0, gate_probes: int = 3) -> float:
+        """khb_build_l1_resident over the loaded Gn table and build offsets: the level-1 bloom and its gate are
+        built on the device and installed there.  Returns the build kernel's ms."""
+        ms = C.c_float(0)
+        _check(self.L.khb_build_l1_resident(self.h, centres, len(centres) // 64, groups_per_job, l1ext, bytes_per_sub,
+                                            bits, hashes, gate_log2, gate_probes, C.byref(ms)), self.h, self.L)
+        return float(ms.value)
+
+    def mem_info(self) -> tuple[int, int, int]:
+        """(free, total, bytes of one submission slot's scratch) of the context's device."""
+        f, t, s = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.L.khb_mem_info(self.h, C.byref(f), C.byref(t), C.byref(s)), self.h, self.L)
+        return int(f.value), int(t.value), int(s.value)
+
+    def resident_bytes(self, which: int) -> int:
+        n = C.c_uint64(0)
+        _check(self.L.khb_resident_bytes(self.h, which, C.byref(n)), self.h, self.L)
+        return int(n.value)
+
+    def resident_read(self, which: int, offset: int = 0, nbytes: int | None = None) -> bytes:
+        """A window of an installed table (TABLE_*); the whole table by default."""
+        if nbytes is None:
+            nbytes = self.resident_bytes(which) - offset
+        out = C.create_string_buffer(max(1, nbytes))
+        _check(self.L.khb_resident_read(self.h, which, offset, nbytes, out), self.h, self.L)
+        return out.raw[:nbytes]
+
+    def resident_popcount(self, which: int) -> int:
+        n = C.c_uint64(0)
+        _check(self.L.khb_resident_popcount(self.h, which, C.byref(n)), self.h, self.L)
+        return int(n.value)
+
+    def gate_probe(self, xs: bytes) -> bytes:
+        """Per 32-byte BE x: bit 0 the full gate passes, bit 1 the stage-1 fold, bit 2 the stage-0 filter."""
+        n = len(xs) // 32
+        out = C.create_string_buffer(n)
+        _check(self.L.khb_gate_probe(self.h, xs, out, n), self.h, self.L)
         return out.raw
 
     # ---- -m address ----

@@ -12,8 +12,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 6                 # include/khhost.h
+KHH_ABI_VERSION = 7                 # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
+KHH_RESIDENT_INFO = 8
+TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
 
 
 class KhhError(RuntimeError):
@@ -40,6 +42,19 @@ def lib() -> C.CDLL:
         L.khh_tables_new_gpu.restype = C.c_void_p
         L.khh_tables_new_gpu.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_int, P(C.c_double), C.c_char_p,
                                          C.c_size_t]
+        L.khh_tables_new_resident.restype = C.c_void_p
+        L.khh_tables_new_resident.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
+                                              P(C.c_double), C.c_char_p, C.c_size_t]
+        L.khh_tables_is_resident.argtypes = [C.c_void_p]
+        L.khh_tables_set_resident_stages.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.khh_resident_gate_log2.restype = C.c_uint32
+        L.khh_resident_gate_log2.argtypes = [C.c_uint64, C.c_uint64]
+        L.khh_resident_keeps_fold.argtypes = [C.c_uint64, C.c_uint32]
+        L.khh_session_resident_info.argtypes = [C.c_void_p, P(C.c_uint64), C.c_uint32]
+        L.khh_session_resident_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, P(C.c_uint64)]
+        L.khh_session_resident_read.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
+        L.khh_session_resident_popcount.argtypes = [C.c_void_p, C.c_uint32, C.c_int, P(C.c_uint64)]
+        L.khh_session_gate_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32]
         L.khh_params.argtypes = [C.c_void_p, P(C.c_uint64)]
         L.khh_bloom.restype = P(C.c_uint8)
         L.khh_bloom.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64), P(C.c_uint64), P(C.c_uint32)]
@@ -128,13 +143,29 @@ class Tables:
 
     def __init__(self, n: str | None = None, k: int = 1, threads: int = 0, gpl: int = 4,
                  files_dir: str | None = None, save: bool = False, skip_checksum: bool = False,
-                 gpu_device: int | None = None):
+                 gpu_device: int | None = None, resident: bool = False, gate_log2: int = 0,
+                 stage1: int = 1, stage0: int = 0):
         """files_dir: -S semantics — read the reference's table files from that directory, compute
-        only what is missing, and with save=True write the missing files back (self.have = mask)."""
+        only what is missing, and with save=True write the missing files back (self.have = mask).
+        resident (with gpu_device): large -k tables, whose level-1 bloom and gate every Session builds on its
+        devices and keeps there; gate_log2 0 = sized from the device's free memory, else an explicit size (log2
+        bits, 13..38); stage1 / stage0 = the gate stages (khb_set_gate_stage1 / khb_set_gate_stage0 values)."""
         err = C.create_string_buffer(256)
         self.have = 0
         self.build_ms = 0.0
-        if gpu_device is not None:
+        self.resident = bool(resident)
+        if resident:
+            if gpu_device is None or files_dir is not None:
+                raise KhhError("resident tables are built on a GPU (gpu_device=...), without table files")
+            ms = C.c_double(0)
+            self.h = lib().khh_tables_new_resident(n.encode() if n else None, k, threads, gpl, gpu_device, gate_log2,
+                                                   C.byref(ms), err, 256)
+            self.build_ms = ms.value
+            if self.h and lib().khh_tables_set_resident_stages(self.h, stage1, stage0):
+                lib().khh_tables_free(self.h)
+                self.h = None
+                raise KhhError("invalid gate stage sizes")
+        elif gpu_device is not None:
             ms = C.c_double(0)
             self.h = lib().khh_tables_new_gpu(n.encode() if n else None, k, threads, gpl, gpu_device, C.byref(ms),
                                               err, 256)
@@ -172,7 +203,16 @@ class Tables:
     def bloom(self, level: int, idx: int) -> tuple[bytes, int, int]:
         nb, bits, h = C.c_uint64(), C.c_uint64(), C.c_uint32()
         p = lib().khh_bloom(self.h, level, idx, C.byref(nb), C.byref(bits), C.byref(h))
+        if not p:
+            raise KhhError("resident tables keep the level-1 bloom on the GPU (Session.resident_read)"
+                           if level == 1 and self.resident else "no such bloom")
         return C.string_at(p, nb.value), int(bits.value), int(h.value)
+
+    def l1_geometry(self) -> tuple[int, int, int]:
+        """(bytes per sub-bloom, bits, hashes) of level 1; also on resident tables."""
+        nb, bits, h = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        lib().khh_bloom(self.h, 1, 0, C.byref(nb), C.byref(bits), C.byref(h))
+        return int(nb.value), int(bits.value), int(h.value)
 
     def bloom_concat(self, level: int = 1) -> tuple[bytes, int, int, int]:
         parts = [self.bloom(level, i)[0] for i in range(256)]
@@ -202,6 +242,8 @@ class Tables:
 
     def gate(self) -> tuple[bytes, int]:
         """The level-0 gate (khb_load_gate) and its log2 size; (b"", 0) when the tables have none."""
+        if self.resident:
+            raise KhhError("resident tables keep the gate on the GPU (Session.resident_read)")
         lg = C.c_uint32(0)
         p = lib().khh_gate(self.h, C.byref(lg))
         return (C.string_at(p, (1 << lg.value) // 8) if lg.value else b""), int(lg.value)
@@ -342,6 +384,50 @@ class Session:
         if rc:
             raise KhhError(f"set_test_hooks failed ({rc})")
 
+    # ---- resident tables and the installed tables of any session (include/khbsgs.h KHB_TABLE_*) ----
+    def resident_info(self) -> list[dict]:
+        """Per device of a session on resident tables: what it built (khh_session_resident_info)."""
+        n = lib().khh_session_resident_info(self.h, None, 0)
+        out = (C.c_uint64 * (KHH_RESIDENT_INFO * max(1, n)))()
+        lib().khh_session_resident_info(self.h, out, n)
+        keys = ("l1_bytes", "gate_log2", "gate_probes", "fold_log2_bytes", "stage0_log2_bytes", "build_ms",
+                "free_bytes", "total_bytes")
+        res = []
+        for i in range(n):
+            d = {k: int(out[KHH_RESIDENT_INFO * i + j]) for j, k in enumerate(keys)}
+            d["build_ms"] = d["build_ms"] / 1e3
+            res.append(d)
+        return res
+
+    def _rc(self, rc: int, what: str) -> None:
+        if rc:
+            raise KhhError(f"{what} failed ({rc})")
+
+    def resident_bytes(self, which: int, device_index: int = 0) -> int:
+        n = C.c_uint64(0)
+        self._rc(lib().khh_session_resident_bytes(self.h, device_index, which, C.byref(n)), "resident_bytes")
+        return int(n.value)
+
+    def resident_read(self, which: int, offset: int = 0, nbytes: int | None = None, device_index: int = 0) -> bytes:
+        """A window of an installed table (TABLE_*) of one device; the whole table by default."""
+        if nbytes is None:
+            nbytes = self.resident_bytes(which, device_index) - offset
+        out = C.create_string_buffer(max(1, nbytes))
+        self._rc(lib().khh_session_resident_read(self.h, device_index, which, offset, nbytes, out), "resident_read")
+        return out.raw[:nbytes]
+
+    def resident_popcount(self, which: int, device_index: int = 0) -> int:
+        n = C.c_uint64(0)
+        self._rc(lib().khh_session_resident_popcount(self.h, device_index, which, C.byref(n)), "resident_popcount")
+        return int(n.value)
+
+    def gate_probe(self, xs: bytes, device_index: int = 0) -> bytes:
+        """Per 32-byte BE x: bit 0 the full gate passes, bit 1 the stage-1 fold, bit 2 the stage-0 filter."""
+        n = len(xs) // 32
+        out = C.create_string_buffer(max(1, n))
+        self._rc(lib().khh_session_gate_probe(self.h, device_index, xs, out, n), "gate_probe")
+        return out.raw[:n]
+
     def recorded(self) -> list[tuple[int, int, int]]:
         """Level-1 candidates of the last run: (chunk base, target index, a)."""
         n = lib().khh_session_recorded(self.h, None, None, None, 0)
@@ -452,3 +538,13 @@ class Addr:
                  for i in range(n)]
         return found, {"chunks": st[0], "keys": st[1], "hits": st[2], "degenerate": st[3], "kernel_s": st[4] / 1e6,
                        "launches": st[5], "shader_mhz": st[6] / 1e3, "rescans": st[7]}
+
+
+def resident_gate_log2(l1ext: int, budget_bytes: int) -> int:
+    """The gate policy of resident builds (Tables::resident_gate_log2): log2 bits, 0 = no gate."""
+    return int(lib().khh_resident_gate_log2(l1ext, budget_bytes))
+
+
+def resident_keeps_fold(l1ext: int, gate_log2: int) -> bool:
+    """Whether a resident build's AUTO stage-1 setting keeps the fold (Tables::resident_keeps_fold)."""
+    return bool(lib().khh_resident_keeps_fold(l1ext, gate_log2))
