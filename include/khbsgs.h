@@ -252,7 +252,10 @@ int khb_dump_x(khb_ctx* ctx, const uint8_t* centre_xy_be, uint32_t group_begin, 
                uint8_t* xs);
 /* Field self-test kernel: r[i] = op(a[i], b[i]) mod p, canonical, for op 0=mul 1=sqr 2=add 3=sub
  * 4=inv 5=lazy add (a < p, b < 2^256) 6=a^2 + b (the fused squaring, a, b < 2^256); 32-byte BE
- * values. */
+ * values.  op | KHB_FIELD_OP_RAW (op 0, 1, 3, 5 or 6; KHB_EINVAL otherwise) returns the value as the device
+ * function leaves it, without the final canonicalisation: congruent mod p and < 2^256, the lazy value the walk
+ * itself carries.  An added op value: no signature or struct changed, so the ABI version stays 7. */
+#define KHB_FIELD_OP_RAW 0x100
 int khb_field_op(khb_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* r, uint32_t n);
 /* Bloom self-test kernel: hit[i] = bloom_check(level-1, x[i]) for 32-byte BE x values. */
 int khb_probe(khb_ctx* ctx, const uint8_t* xs, uint8_t* hit, uint32_t n);

@@ -75,12 +75,13 @@ __global__ void k_hash160(const Fe* __restrict__ xy, int kind, const uint8_t* __
   o[20] = bloom ? (bloom_check20(bloom, g, h) ? 1 : 0) : 0;
 }
 
-// Field self-test: the fast (fe_asm.hpp) operations, results canonicalised.
+// Field self-test: the fast (fe_asm.hpp) operations, results canonicalised; op | KHB_FIELD_OP_RAW leaves the
+// value as the function returned it (lazy, < 2^256).
 __global__ void k_field_op(int op, const Fe* __restrict__ a, const Fe* __restrict__ b, Fe* __restrict__ r, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Fe x = a[i], y = b[i], z;
-  switch (op) {
+  switch (op & ~KHB_FIELD_OP_RAW) {
     case 0: fm_mul(z, x, y); break;
     case 1: fm_sqr(z, x); break;
     case 2: fm_add(z, x, y); break;
@@ -89,7 +90,7 @@ __global__ void k_field_op(int op, const Fe* __restrict__ a, const Fe* __restric
     case 6: fm_sqr_add(z, x, y); break;      // x, y < 2^256
     default: fm_inv(z, x); break;
   }
-  fm_canon(z, z);
+  if (!(op & KHB_FIELD_OP_RAW)) fm_canon(z, z);
   r[i] = z;
 }
 
@@ -915,7 +916,11 @@ int khb_dump_x(khb_ctx* c, const uint8_t* centre, uint32_t group_begin, uint32_t
 }
 
 int khb_field_op(khb_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* r, uint32_t n) {
+  const int raw = op & KHB_FIELD_OP_RAW;
+  op &= ~KHB_FIELD_OP_RAW;
   if (!c || !a || !r || n == 0 || op < 0 || op > 6 || (op != 1 && op != 4 && !b)) return KHB_EINVAL;
+  if (raw && (op == 2 || op == 4)) return KHB_EINVAL;   // fm_add is canonical by contract; fm_inv's lazy value is not pinned
+  op |= raw;
   KHB_TRY(c, hipSetDevice(c->device));
   Slot& S = c->slot[0];
   Fe* h = (Fe*)malloc(sizeof(Fe) * n * 3);

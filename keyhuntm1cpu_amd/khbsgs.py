@@ -60,6 +60,7 @@ class Stats(C.Structure):
 _libs: dict[str, C.CDLL] = {}
 KHB_ABI_VERSION = 7
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
+FIELD_OP_RAW = 0x100                                             # include/khbsgs.h KHB_FIELD_OP_RAW
 
 
 def lib(path: str | None = None) -> C.CDLL:
@@ -281,6 +282,7 @@ class Engine:
         return out.raw
 
     def field_op(self, op: int, a: bytes, b: bytes | None) -> bytes:
+        """khb_field_op; op | FIELD_OP_RAW (op 0, 1, 3, 5, 6) returns the lazy value, not canonicalised."""
         n = len(a) // 32
         out = C.create_string_buffer(n * 32)
         _check(self.L.khb_field_op(self.h, op, a, b, out, n), self.h, self.L)

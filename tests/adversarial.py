@@ -1,0 +1,461 @@
+"""Directed inputs for the rare-carry, canonicalisation and degenerate paths (test infrastructure).
+
+Three things live here, all on Python integers:
+
+  * secp256k1 affine arithmetic and finders of curve points whose x (or y) falls in a class that the
+    lazy field arithmetic of csrc/device/fe_asm.hpp treats specially;
+  * a limb-level model of that arithmetic (fm_reduce, fm_reduce_add, fm_reduce_T, fm_sub, fm_add_lazy,
+    fm_canon) that mirrors the header's decomposition (T, P_i, R, top, u, w, w2) and reports which rare
+    branch a given operand needs.  The model is never the expected value of a test: it chooses operands
+    and certifies that each one arithmetically requires the branch it is aimed at;
+  * planting: start points such that a chosen step of a chosen group of the walk lands on a chosen point,
+    the reference's rule for a group's centre, and a reference of one -m address group from a centre.
+"""
+from __future__ import annotations
+
+import random
+
+P = 2**256 - 2**32 - 977
+N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+K = 2**32 + 977                      # 2^256 mod p
+M32 = 0xFFFFFFFF
+GROUP = 1024
+HALF = 512
+
+# ---------------------------------------------------------------------------------- curve arithmetic
+
+
+def inv(a: int) -> int:
+    """a^(p-2): the inverse, and 0 for 0 as the reference's ModInv."""
+    return pow(a, P - 2, P)
+
+
+def on_curve(pt) -> bool:
+    x, y = pt
+    return 0 <= x < P and 0 <= y < P and (y * y - x * x * x - 7) % P == 0
+
+
+def neg(pt):
+    return None if pt is None else (pt[0], (P - pt[1]) % P)
+
+
+def add(p1, p2):
+    """Affine addition; None is the point at infinity."""
+    if p1 is None:
+        return p2
+    if p2 is None:
+        return p1
+    x1, y1 = p1
+    x2, y2 = p2
+    if x1 == x2:
+        if (y1 + y2) % P == 0:
+            return None
+        s = 3 * x1 * x1 * inv(2 * y1) % P
+    else:
+        s = (y2 - y1) * inv(x2 - x1) % P
+    x3 = (s * s - x1 - x2) % P
+    return x3, (s * (x1 - x3) - y1) % P
+
+
+def sqrt(v: int):
+    """v^((p+1)/4) (p = 3 mod 4), or None when v is no square."""
+    r = pow(v % P, (P + 1) // 4, P)
+    return r if r * r % P == v % P else None
+
+
+def cbrt(a: int):
+    """a^((p+2)/9) (p = 7 mod 9: its cube is a^((p-1)/3) * a), or None when a is no cube."""
+    r = pow(a % P, (P + 2) // 9, P)
+    return r if pow(r, 3, P) == a % P else None
+
+
+def lift_x(x: int, odd: int = 0):
+    y = sqrt(x * x * x + 7)
+    if y is None:
+        return None
+    return (x, y if (y & 1) == odd else P - y)
+
+
+# ------------------------------------------------------------------------------------- point finders
+# class A: x < K                  the lazy product leaves the reduction as x + p (top word ffffffff)
+# class B: K <= x < K + 2^40      the reduction's rare branch and its fold of a wrap past 2^256
+# class C: x mod 2^96 < 2^33      the rare branch (carry out of limb 2 of the second fold)
+# class D: 2^256 - 2^224 <= x < p top word ffffffff with a canonical value
+# class Y: y < K
+
+def in_class(cls: str, pt) -> bool:
+    x, y = pt
+    if cls == "A":
+        return x < K
+    if cls == "B":
+        return K <= x < K + 2**40
+    if cls == "C":
+        return x % 2**96 < 2**33 and x >= K + 2**40
+    if cls == "D":
+        return 2**256 - 2**224 <= x < P
+    if cls == "Y":
+        return y < K
+    raise ValueError(cls)
+
+
+def class_values(cls: str, seed: int = 0):
+    """An endless stream of field values (not necessarily x of a point) of class A, B, C or D."""
+    rng = random.Random(f"{cls}{seed}")
+    i = 0
+    while True:
+        if cls == "A":
+            v = i if i < 64 else rng.randrange(K)
+        elif cls == "B":
+            v = K + i if i < 64 else K + rng.randrange(2**40)
+        elif cls == "C":
+            v = (rng.randrange(1, 2**160) << 96) | rng.randrange(2**33)
+        elif cls == "D":
+            v = P - 1 - i if i < 64 else (M32 << 224) | rng.randrange(2**224)
+        else:
+            raise ValueError(cls)
+        i += 1
+        if v < P:
+            yield v
+
+
+def class_points(cls: str, n: int, seed: int = 0) -> list:
+    """n distinct curve points of the class, the same for the same seed."""
+    out = []
+    if cls == "Y":
+        y = 0
+        while len(out) < n:
+            x = cbrt(y * y - 7)
+            if x is not None:
+                out.append((x, y))
+            y += 1
+        return out
+    seen = set()
+    for k, v in enumerate(class_values(cls, seed)):
+        if v in seen:
+            continue
+        seen.add(v)
+        pt = lift_x(v, k & 1)
+        if pt is not None:
+            out.append(pt)
+            if len(out) == n:
+                return out
+
+
+# ------------------------------------------------------------- limb-level model of device/fe_asm.hpp
+
+def limbs(v: int, n: int = 8) -> list:
+    return [(v >> (32 * i)) & M32 for i in range(n)]
+
+
+def value(w) -> int:
+    return sum(x << (32 * i) for i, x in enumerate(w))
+
+
+def _propagate(r: list, k: int, c: int) -> int:
+    """fm_propagate<K>: r[k..7] += c, carry-out returned."""
+    for i in range(k, 8):
+        t = r[i] + c
+        r[i] = t & M32
+        c = t >> 32
+    return c
+
+
+def m_reduce_T(T: list, H: list):
+    """fm_reduce_T: T (10 words, T9:T8 <= 2^32 + 1) + 977*H -> (lazy value, c3, wrap)."""
+    Pi = [977 * H[i] + T[i] for i in range(8)]
+    R = [Pi[0] & M32]
+    c = 0
+    for i in range(1, 8):
+        t = (Pi[i] & M32) + (Pi[i - 1] >> 32) + c
+        R.append(t & M32)
+        c = t >> 32
+    t = T[8] + (Pi[7] >> 32) + c
+    R8, c = t & M32, t >> 32
+    t = T[9] + c
+    R9 = t & M32
+    assert t >> 32 == 0 and (R9 << 32 | R8) < 3 * 2**32
+    u = R8 * 977 + (((R9 * 977) & M32) << 32)
+    w = ((u >> 32) & M32) + R8
+    w2 = ((w >> 32) + R9) & M32
+    t = R[0] + (u & M32)
+    R[0], c = t & M32, t >> 32
+    t = R[1] + (w & M32) + c
+    R[1], c = t & M32, t >> 32
+    t = R[2] + w2 + c
+    R[2], c3 = t & M32, t >> 32
+    wrap = 0
+    if c3:
+        wrap = _propagate(R, 3, c3)
+        t = R[0] + wrap * 977
+        R[0] = t & M32
+        t = R[1] + wrap + (t >> 32)
+        R[1] = t & M32
+        _propagate(R, 2, t >> 32)
+    return value(R), c3, wrap
+
+
+def m_reduce(t: int):
+    """fm_reduce of a 512-bit product: T = L + (H << 32) as 10 words."""
+    L, H = limbs(t & (2**256 - 1)), limbs(t >> 256)
+    T = [L[0]]
+    c = 0
+    for i in range(1, 8):
+        s = L[i] + H[i - 1] + c
+        T.append(s & M32)
+        c = s >> 32
+    s = H[7] + c
+    T.append(s & M32)
+    T.append(s >> 32)
+    return m_reduce_T(T, H)
+
+
+def m_reduce_add(t: int, w: int):
+    """fm_reduce_add: T = (L + w) + (H << 32), w < 2^256."""
+    L, H, W = limbs(t & (2**256 - 1)), limbs(t >> 256), limbs(w)
+    U = []
+    c = 0
+    for i in range(8):
+        s = L[i] + W[i] + c
+        U.append(s & M32)
+        c = s >> 32
+    U.append(c)
+    T = [U[0]]
+    c = 0
+    for i in range(1, 9):
+        s = U[i] + H[i - 1] + c
+        T.append(s & M32)
+        c = s >> 32
+    T.append(c)
+    return m_reduce_T(T, H)
+
+
+def m_mul(a: int, b: int):
+    return m_reduce(a * b)
+
+
+def m_sqr(a: int, _b: int = 0):
+    return m_reduce(a * a)
+
+
+def m_sqr_add(a: int, w: int):
+    return m_reduce_add(a * a, w)
+
+
+def m_sub(a: int, b: int):
+    """fm_sub(a < 2^256, b < p) -> (value, sub_b2)."""
+    A, B = limbs(a), limbs(b)
+    d = []
+    bo = 0
+    for i in range(8):
+        t = A[i] - B[i] - bo
+        d.append(t & M32)
+        bo = 1 if t < 0 else 0
+    m = M32 if bo else 0
+    t = d[0] - (m & 0x3D1)
+    d[0], bo = t & M32, (1 if t < 0 else 0)
+    t = d[1] - (m & 1) - bo
+    d[1], b2 = t & M32, (1 if t < 0 else 0)
+    bo = b2
+    for i in range(2, 8):
+        t = (d[i] - bo) & M32
+        bo = 1 if (bo and d[i] == 0) else 0
+        d[i] = t
+    return value(d), b2
+
+
+def m_add_lazy(a: int, b: int):
+    """fm_add_lazy(a < p, b < 2^256) -> (value, lazy_c2)."""
+    A, B = limbs(a), limbs(b)
+    s = []
+    c = 0
+    for i in range(8):
+        t = A[i] + B[i] + c
+        s.append(t & M32)
+        c = t >> 32
+    t = s[0] + 0x3D1 * c
+    s[0] = t & M32
+    t = s[1] + c + (t >> 32)
+    s[1], c2 = t & M32, t >> 32
+    _propagate(s, 2, c2)
+    return value(s), c2
+
+
+def m_canon(a: int) -> int:
+    """fm_canon: a + K carries out of 2^256 iff a >= p."""
+    t = a + K
+    return t & (2**256 - 1) if t >> 256 else a
+
+
+# field self-test op numbers (include/khbsgs.h khb_field_op) -> model, exact value
+MODEL = {0: m_mul, 1: m_sqr, 3: m_sub, 5: m_add_lazy, 6: m_sqr_add}
+EXACT = {0: lambda a, b: a * b % P, 1: lambda a, b: a * a % P, 3: lambda a, b: (a - b) % P,
+         5: lambda a, b: (a + b) % P, 6: lambda a, b: (a * a + b) % P}
+
+
+def flags(op: int, a: int, b: int) -> dict:
+    r = MODEL[op](a, b)
+    if op in (0, 1, 6):
+        return {"c3": r[1], "wrap": r[2]}
+    return {"sub_b2": r[1]} if op == 3 else {"lazy_c2": r[1]}
+
+
+def random_operands(op: int, rng: random.Random):
+    """An ordinary operand pair within the op's contract (fe_asm.hpp)."""
+    if op in (0, 1):
+        return rng.randrange(2**256), rng.randrange(2**256)
+    if op == 3:
+        return rng.randrange(2**256), rng.randrange(P)
+    if op == 5:
+        return rng.randrange(P), rng.randrange(2**256)
+    return rng.randrange(2**256), rng.randrange(2**256)
+
+
+# --------------------------------------------------------------------------------- operand generators
+
+def directed_operands(op: int, flag: str, n: int, seed: int = 0) -> list:
+    """n operand pairs (a, b) of op that need the branch `flag` by the model.  Candidates are built so that
+    the exact result has the shape the branch fires on and kept only when the model's flag is set."""
+    rng = random.Random(f"{op}{flag}{seed}")
+    out = []
+    if op in (0, 1, 6):
+        vals = class_values("B" if flag == "wrap" else "C", seed)
+        while len(out) < n:
+            v = next(vals)
+            if op == 0:
+                a = rng.randrange(1, P)
+                if rng.random() < 0.25:
+                    a = P + rng.randrange(1, K)     # a lazy operand >= p
+                b = v * inv(a) % P
+            elif op == 1:
+                a = sqrt(v)
+                if a is None:
+                    continue
+                a, b = (P - a if rng.random() < 0.5 else a), 0
+            else:
+                b = rng.randrange(2**256)
+                a = sqrt(v - b)
+                if a is None:
+                    continue
+            if flags(op, a, b)[flag] and (flag == "wrap" or not flags(op, a, b)["wrap"]):
+                out.append((a, b))
+        return out
+    if op == 3:
+        # a < b and (a - b) mod 2^64 < K: adding p back borrows out of limb 1.  d = a - b + 2^256.
+        while len(out) < n:
+            shape = len(out) % 4
+            d = rng.randrange(2**256) & ~(2**64 - 1) | rng.randrange(K)
+            if shape == 1:
+                d &= ~(M32 << 64)                  # limb 2 zero: the borrow runs on into limb 3
+            elif shape == 2:
+                d &= ~((2**96 - 1) << 64)          # limbs 2..4 zero
+            elif shape == 3:
+                d = (1 << 255) | (d & (2**64 - 1)) # limbs 2..6 zero
+            lo = 2**256 - d
+            if lo >= P:
+                continue
+            b = rng.randrange(lo, P)
+            a = b + d - 2**256
+            if flags(3, a, b)[flag]:
+                out.append((a, b))
+        return out
+    if op == 5:
+        # a + b = 2^256 + s with s mod 2^64 >= 2^64 - K: folding the carry carries out of limb 1
+        while len(out) < n:
+            shape = len(out) % 4
+            a = rng.randrange(2**200, P)
+            s = rng.randrange(a) & ~(2**64 - 1) | (2**64 - 1 - rng.randrange(K))
+            if shape == 1:
+                s |= M32 << 64                     # limb 2 all ones: the carry runs on into limb 3
+            elif shape == 2:
+                s |= (2**96 - 1) << 64
+            elif shape == 3:
+                s |= (2**160 - 1) << 64
+            if s >= a:
+                continue
+            b = s + 2**256 - a
+            if flags(5, a, b)[flag]:
+                out.append((a, b))
+        return out
+    raise ValueError(op)
+
+
+# ------------------------------------------------------------------------------------------ planting
+
+def be64(pt) -> bytes:
+    return pt[0].to_bytes(32, "big") + pt[1].to_bytes(32, "big")
+
+
+def table_points(raw: bytes) -> list:
+    """The 513 affine points of a giant table (GSn[0..511], _2GSn), x||y big-endian."""
+    return [(int.from_bytes(raw[64 * i:64 * i + 32], "big"), int.from_bytes(raw[64 * i + 32:64 * i + 64], "big"))
+            for i in range(len(raw) // 64)]
+
+
+def group_offset(ora, bs, g: int):
+    """g * _2GSn as helpers.lane_offsets builds it: -(g * 2048 * M) * G."""
+    if g == 0:
+        return None
+    return ora.negation(ora.pubkey(g * 2048 * bs.m)).xy()
+
+
+def step_of(i: int, sign: int) -> int:
+    """The step t of a group at which C + sign * GSn[i] stands (t = 512 is C itself: i = -1)."""
+    if i < 0:
+        return HALF
+    return HALF - 1 - i if sign < 0 else HALF + 1 + i
+
+
+def planted_cases():
+    """(i, sign) of the 14 planted steps: i in {511, 510, 509, 3, 2, 1, 0} with both signs where the step has
+    both (C + GSn[511] is not part of a group), and the centre itself (i = -1)."""
+    cases = [(511, -1)]
+    for i in (510, 509, 3, 2, 1, 0):
+        cases += [(i, -1), (i, +1)]
+    return cases + [(-1, 0)]
+
+
+def centre_for(Q, i: int, sign: int, gsn: list):
+    """The centre C with C + sign * GSn[i] == Q (i = -1: C = Q)."""
+    if i < 0:
+        return Q
+    return add(Q, gsn[i]) if sign < 0 else add(Q, neg(gsn[i]))
+
+
+def start_for(centre, g: int, ora, bs):
+    """startP such that group g's centre, startP + g * _2GSn, is `centre`."""
+    return add(centre, neg(group_offset(ora, bs, g)))
+
+
+def ref_centre(ora, bs, start, g: int):
+    """The reference's centre of group g of a job that starts at `start`: AddDirect(startP, g * _2GSn) with
+    ModInv(0) = 0 (so it also defines the collapsed add); group 0 is startP itself.  An ora.Point."""
+    sp = ora.Point.of(*start)
+    if g == 0:
+        return sp
+    return ora.add_direct(sp, ora.Point.of(*group_offset(ora, bs, g)))
+
+
+def addr_group_ref(centre, gn: list):
+    """One -m address group from its centre C with the table Gn[0..511], _2Gn (keyhunt.cpp:2586-2711):
+    pts[t] = C - Gn[511 - t] (t < 512), C (t = 512), C + Gn[t - 513] (t > 512) as x||y, and the next centre
+    C + _2Gn.  Plain chord additions (C is never +-Gn[i]) with the 513 inverses from one batch inversion."""
+    cx, cy = centre
+    dx = [(g[0] - cx) % P for g in gn]
+    assert all(dx)
+    pre = [1]
+    for d in dx:
+        pre.append(pre[-1] * d % P)
+    acc = inv(pre[-1])
+    inverse = [0] * len(dx)
+    for i in range(len(dx) - 1, -1, -1):
+        inverse[i] = acc * pre[i] % P
+        acc = acc * dx[i] % P
+
+    def chord(i, sign):
+        gx, gy = gn[i][0], gn[i][1] if sign > 0 else P - gn[i][1]
+        s = (gy - cy) * inverse[i] % P
+        x = (s * s - cx - gx) % P
+        return x, (s * (cx - x) - cy) % P
+
+    out = [chord(HALF - 1 - t, -1) for t in range(HALF)] + [centre] + [chord(t, +1) for t in range(HALF - 1)]
+    return b"".join(be64(p) for p in out), chord(HALF, +1)

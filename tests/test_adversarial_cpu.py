@@ -1,0 +1,187 @@
+"""tests/adversarial.py checked on the CPU: the point finders, the limb model of fe_asm.hpp's lazy arithmetic
+against Python big integers, the operand generators (every operand must need its branch), planting against
+the oracle's walk, and the -m address group reference against the oracle's.  Exact equality throughout."""
+from __future__ import annotations
+
+import random
+
+import pytest
+
+from tests import adversarial as adv
+
+P, K = adv.P, adv.K
+OPS = (0, 1, 3, 5, 6)
+DIRECTED = ((0, "c3"), (0, "wrap"), (1, "c3"), (1, "wrap"), (6, "c3"), (6, "wrap"), (3, "sub_b2"), (5, "lazy_c2"))
+
+
+@pytest.fixture(scope="module")
+def bs32(ora):
+    b = ora.Bsgs("0x100000000", 1)
+    yield b
+    b.close()
+
+
+def test_curve_arithmetic():
+    g = (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
+         0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)
+    assert adv.on_curve(g) and not adv.on_curve((g[0], g[1] + 1))
+    g2 = adv.add(g, g)
+    assert g2[0] == 0xC6047F9441ED7D6D3045406E95C07CD85C778E4B8CEF3CA7ABAC09B95C709EE5 and adv.on_curve(g2)
+    assert adv.add(g2, adv.neg(g)) == g and adv.add(g, adv.neg(g)) is None and adv.add(None, g) == g
+    assert adv.add(adv.add(g2, g), g) == adv.add(g2, g2)
+    assert adv.sqrt(9) in (3, P - 3) and adv.sqrt(g[0]**3 + 7) in (g[1], P - g[1])
+    assert adv.cbrt(27) is not None and pow(adv.cbrt(27), 3, P) == 27
+    assert P % 9 == 7 and P % 4 == 3
+    assert sum(adv.cbrt(a) is None for a in range(2, 200)) > 100      # two thirds of all values are no cubes
+    assert adv.inv(0) == 0 and adv.inv(5) * 5 % P == 1
+
+
+@pytest.mark.parametrize("cls", ["A", "B", "C", "D", "Y"])
+def test_point_classes(cls):
+    pts = adv.class_points(cls, 12, seed=3)
+    assert len(pts) >= 8 and len(set(pts)) == len(pts)
+    for pt in pts:
+        assert adv.on_curve(pt) and adv.in_class(cls, pt), (cls, pt)
+    assert pts == adv.class_points(cls, 12, seed=3)
+    if cls == "D":
+        assert all(pt[0] >> 224 == 0xFFFFFFFF for pt in pts)
+
+
+def test_known_small_points():
+    """The issue's census: 101 of the x in [0, 200) and 113 of the 200 x below p are on the curve, and
+    0x1000003d0 / 0x1000003d2 straddle K."""
+    assert sum(adv.lift_x(x) is not None for x in range(200)) == 101
+    assert all(adv.lift_x(x) is not None for x in (1, 2, 3, 4, 6, 8))
+    assert sum(adv.lift_x(P - 1 - i) is not None for i in range(200)) == 113
+    assert adv.lift_x(0x1000003D0) is not None and adv.lift_x(0x1000003D2) is not None
+    assert 0x1000003D0 < K < 0x1000003D2
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_model_is_congruent_and_lazy(op):
+    """100,000 seeded random operand pairs within the op's contract: congruent, < 2^256, and fm_canon of it is
+    the canonical value."""
+    rng = random.Random(1000 + op)
+    model, exact = adv.MODEL[op], adv.EXACT[op]
+    for _ in range(100000):
+        a, b = adv.random_operands(op, rng)
+        r = model(a, b)[0]
+        e = exact(a, b)
+        assert 0 <= r < 2**256 and r % P == e and adv.m_canon(r) == e, (op, a, b)
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_no_flag_on_random_operands(op):
+    rng = random.Random(2000 + op)
+    for _ in range(10000):
+        a, b = adv.random_operands(op, rng)
+        assert not any(adv.flags(op, a, b).values()), (op, a, b)
+
+
+@pytest.mark.parametrize("op,flag", DIRECTED)
+def test_directed_operands_need_their_branch(op, flag):
+    n = 256 if op in (0, 1, 6) else 64
+    ops = adv.directed_operands(op, flag, n, seed=1)
+    assert len(ops) == n and len(set(ops)) == n
+    for a, b in ops:
+        assert a < 2**256 and b < 2**256
+        if op == 3:
+            assert b < P
+        if op == 5:
+            assert a < P
+        assert adv.flags(op, a, b)[flag] == 1, (op, flag, a, b)
+        r = adv.MODEL[op](a, b)[0]
+        assert r < 2**256 and adv.m_canon(r) == adv.EXACT[op](a, b)
+    assert ops == adv.directed_operands(op, flag, n, seed=1)
+
+
+def test_sub_and_lazy_add_shapes_run_the_long_chain():
+    """The directed fm_sub / fm_add_lazy operands include borrows / carries that run through limbs 2..6."""
+    for a, b in adv.directed_operands(3, "sub_b2", 8):
+        assert a < b
+    long_sub = [(a - b) % 2**256 >> 64 & (2**160 - 1) for a, b in adv.directed_operands(3, "sub_b2", 8)]
+    assert 0 in long_sub
+    long_add = [(a + b) % 2**256 >> 64 & (2**160 - 1) for a, b in adv.directed_operands(5, "lazy_c2", 8)]
+    assert 2**160 - 1 in long_add
+
+
+@pytest.mark.parametrize("op", [0, 1, 6])
+def test_class_a_and_b_results(op):
+    """A product whose canonical value v is below K leaves the reduction as v + p (a lazy value >= p with top
+    word ffffffff); v in [K, K + 2^40) always takes the rare branch and its wrap fold and comes out as v.  Both
+    for every product whose first fold L + H*K reaches 2^257 (see below): of random operands, all."""
+    rng = random.Random(3000 + op)
+    for cls in ("A", "B"):
+        vals = adv.class_values(cls, 9)
+        done = 0
+        while done < 500:
+            v = next(vals)
+            if op == 0:
+                a = rng.randrange(1, P)
+                b = v * adv.inv(a) % P
+            else:
+                b = rng.randrange(2**256) if op == 6 else 0
+                a = adv.sqrt(v - b)
+                if a is None:
+                    continue
+                a = P - a if done & 1 else a
+            t = a * b if op == 0 else a * a + b
+            if (t % 2**256) + (t >> 256) * K < 2**257:
+                # v + m*p with the first fold L + H*K below 2^257 can be v itself or 2^256 + (v - K): nothing
+                # is left to fold (1 * 1 = 1; 2^128 squares to 2^256 = K exactly).  No other product is.
+                continue
+            r, c3, wrap = adv.MODEL[op](a, b)
+            if cls == "A":
+                assert r == v + P and r >> 224 == 0xFFFFFFFF and not wrap, (op, v)
+            else:
+                assert r == v and c3 and wrap, (op, v)
+            done += 1
+
+
+def test_class_c_values_take_the_rare_branch():
+    rng = random.Random(5)
+    vals = adv.class_values("C", 2)
+    for _ in range(2000):
+        v = next(vals)
+        if v < K + 2**40:
+            continue
+        a = rng.randrange(1, P)
+        r, c3, wrap = adv.m_mul(a, v * adv.inv(a) % P)
+        assert c3 and not wrap and r == v
+
+
+@pytest.mark.parametrize("cls", ["A", "B", "C", "D"])
+def test_planted_points_appear_in_the_oracle_walk(ora, bs32, cls):
+    gsn = adv.table_points(bs32.giant_table())
+    cases = adv.planted_cases()
+    assert sorted(adv.step_of(i, s) for i, s in cases) == \
+        [0, 1, 2, 508, 509, 510, 511, 512, 513, 514, 515, 516, 1022, 1023]
+    pts = adv.class_points(cls, len(cases), seed=11)
+    for k, ((i, sign), Q) in enumerate(zip(cases, pts)):
+        g = k % 4
+        centre = adv.centre_for(Q, i, sign, gsn)
+        start = adv.start_for(centre, g, ora, bs32)
+        assert adv.on_curve(start)
+        assert adv.ref_centre(ora, bs32, start, g).xy() == centre
+        _, xs, _ = bs32.scan(ora.Point.of(*start), 0, g + 1, want_x=True)
+        a = 1024 * g + adv.step_of(i, sign)
+        assert xs[32 * a:32 * a + 32] == Q[0].to_bytes(32, "big"), (cls, i, sign, g)
+        # the one-group walk from the reference centre gives the same group
+        _, x1, _ = bs32.scan(adv.ref_centre(ora, bs32, start, g), 0, 1, want_x=True)
+        assert x1 == xs[32 * 1024 * g:]
+
+
+def test_addr_group_reference_matches_oracle(ora):
+    gen = ora.AddrGen(1)
+    O = ora.AddrTable("00" * 20 + "\n")
+    try:
+        gn = adv.table_points(gen.table())
+        for key in (0x123456789ABCDEF0123, adv.N - 5000):
+            _, _, ref = gen.group(O, key, 2, want_xy=True)
+            centre = ora.pubkey(key + 512).xy()
+            got, nxt = adv.addr_group_ref(centre, gn)
+            assert got == ref
+            assert nxt == ora.pubkey(key + 512 + 1024).xy()
+    finally:
+        gen.close()
+        O.close()
