@@ -9,9 +9,15 @@
 // wait state before a VALU reads that VCC as carry-in — hipcc pads its own chains with `s_nop 0`
 // (seen in its ISA for __builtin_addc), but nothing inside an asm string is padded
 // (cdna_hip_programming.md §5.7 item 2), so every carry consumer below is preceded by `s_nop 0`.
+// The reduction's V mads (fm_madv) write their carry-out to SGPR pairs instead of VCC.  Those masks are
+// read by the scalar unit on the common path (s_or_b64 / s_cmp: interlocked, no pad) and, in the
+// wave-uniform carry fix only, by v_cndmask as its select mask: a VALU read of a VALU-written SGPR,
+// which fm_fix_R pads with `s_nop 1` on top of the whole R chain that already lies between the two.
 //
 // Value contract (checked by tests/test_gpu_scan.py::test_field_ops and every x-dump test):
 //   * fm_mul / fm_sqr return a value < 2^256 congruent to a*b mod p, not necessarily < p ("lazy").
+//     The lazy value is a function of the operands alone: the same for every lane whether or not its
+//     wave took a rare branch or the reduction's carry fix (tests/test_gpu_field_reduce.py, raw mode).
 //   * fm_sub(a, b) is correct for a < 2^256 and b < p; its result is < 2^256 (< p if it borrowed).
 //   * fm_add(a, b) needs a, b < p and returns a canonical value.
 //   * fm_canon brings any value < 2^256 into [0, p).  Values that are hashed, compared or used as a
@@ -247,108 +253,39 @@ FM_DEV void fm_sqr512x(uint32_t t[16], const uint32_t* a) {
   for (int i = 0; i < 16; ++i) t[i] = u[i];
 }
 
-// Second stage of the reduction: T = L + (H << 32) (+ addend) as 10 words with T9:T8 <= 2^32 + 1,
-// H = the high half of the product; returns a value < 2^256 congruent to T + 977*H.
-FM_DEV void fm_reduce_T(Fe& r, const uint32_t T[10], const uint32_t* H);
+// ---- reduction mod p: 2^256 = 2^32 + 977 applied limb by limb ---------------------------------
+// With L, H the halves of the 512-bit product (Lw = L, or L + w for fm_reduce_add, with its carry
+// Lw8), the value to fold is  S = Lw + Lw8 2^256 + (H << 32) + 977 H.  Per limb that is
+//   V_i = 977 H_i + (H_i : Lw_i)                                     (sum_i V_i 2^(32i) + Lw8 2^256 == S)
+// one v_mad_u64_u32 whose 64-bit addend is the register pair {lo = Lw_i, hi = H_i}: no carry chain
+// for Lw + (H << 32) and no zero-extended addend.  V_i < 2^64 + 977 2^32, so the mad carries out
+// when H_i >= ~2^32 - 978 (2^-22 per limb for random limbs, certain for operands near p).  Each mad
+// writes its carry-out to an SGPR pair of its own (not VCC); the eight lane masks are ORed on the
+// scalar unit.  The chain R = sum_i lo64(V_i) 2^(32i) + Lw8 2^256 then runs on the truncated V_i, and
+// when any lane of the wave carried, a wave-uniform branch adds the dropped carries back: the one
+// out of V_i weighs 2^(32(i+2)), so it is a 0/1 addend of R's word i+2 (fm_fix_R, one chain over
+// words 2..9; a no-op for lanes that did not carry).  After it R is S as 10 words, which is the
+// representation the T = Lw + (H << 32), P_i = 977 H_i + T_i form of this reduction produced, so
+// the second fold and the value returned (lazy, < 2^256) are bit for bit what they were.
+#if KHB_RARE_FORCE
+FM_DEV bool fm_any_mask(uint64_t) { return true; }
+#else
+FM_DEV bool fm_any_mask(uint64_t m) { return __builtin_expect(m != 0, 0); }
+#endif
 
-// Reduce t (512 bits) mod p to a value < 2^256 (lazy).  2^256 = 2^32 + 977 (mod p).
-FM_DEV void fm_reduce(Fe& r, const uint32_t t[16]) {
-  const uint32_t* L = t;
-  const uint32_t* H = t + 8;
-  // T = L + (H << 32): 9 limbs + T9 (both operands near p make L + H*2^32 reach 2^288)
-  uint32_t T[10];
-  asm("v_mov_b32 %0, %10\n\t"
-      "v_add_co_u32_e32 %1, vcc, %11, %18\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %12, %19, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %13, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %14, %21, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %15, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %16, %23, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %17, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %9, vcc, 0, %26, vcc"
-      : "=&v"(T[0]), "=&v"(T[1]), "=&v"(T[2]), "=&v"(T[3]), "=&v"(T[4]), "=&v"(T[5]), "=&v"(T[6]), "=&v"(T[7]),
-        "=&v"(T[8]), "=&v"(T[9])
-      : "v"(L[0]), "v"(L[1]), "v"(L[2]), "v"(L[3]), "v"(L[4]), "v"(L[5]), "v"(L[6]), "v"(L[7]),
-        "v"(H[0]), "v"(H[1]), "v"(H[2]), "v"(H[3]), "v"(H[4]), "v"(H[5]), "v"(H[6]), "v"(H[7]), "v"(0u)
-      : "vcc");
-  fm_reduce_T(r, T, H);
+// V = 977*h + (h : lw); ov = lane mask of the carry-out.  977 comes from an SGPR (VOP3 takes no
+// literal on gfx9; one scalar source per instruction is the constant-bus limit).
+FM_DEV void fm_madv(uint64_t& V, uint64_t& ov, uint32_t h, uint32_t lw, uint32_t k977) {
+  const uint64_t hl = ((uint64_t)h << 32) | lw;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(V), "=s"(ov) : "v"(h), "s"(k977), "v"(hl));
 }
 
-// (t + w) mod p, lazy (< 2^256), for t a 512-bit product and any w < 2^256: the addend rides in
-// the reduction's first carry chain, so a following modular add/sub (x = s^2 - u) costs 9
-// instructions instead of 19.  T = (L + w) + (H << 32) < 2^288 + 2^257: T9:T8 <= 2^32 + 1, the
-// same bound fm_reduce_T relies on.
-FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
-  const uint32_t* L = t;
-  const uint32_t* H = t + 8;
-  uint32_t U[9], T[10];
-  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
+// R9:R8:R[7..0] = sum_i V_i 2^(32i) + T8 2^256 : one carry chain.
+FM_DEV void fm_chain_R(uint32_t R[8], uint32_t& R8, uint32_t& R9, const uint64_t V[8], uint32_t T8) {
+  R[0] = (uint32_t)V[0];
+  asm("v_add_co_u32_e32 %0, vcc, %9, %10\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
-      : "=&v"(U[0]), "=&v"(U[1]), "=&v"(U[2]), "=&v"(U[3]), "=&v"(U[4]), "=&v"(U[5]), "=&v"(U[6]), "=&v"(U[7]),
-        "=&v"(U[8])
-      : "v"(L[0]), "v"(L[1]), "v"(L[2]), "v"(L[3]), "v"(L[4]), "v"(L[5]), "v"(L[6]), "v"(L[7]),
-        "v"(w.v[0]), "v"(w.v[1]), "v"(w.v[2]), "v"(w.v[3]), "v"(w.v[4]), "v"(w.v[5]), "v"(w.v[6]), "v"(w.v[7]),
-        "v"(0u)
-      : "vcc");
-  T[0] = U[0];
-  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
-      : "=&v"(T[1]), "=&v"(T[2]), "=&v"(T[3]), "=&v"(T[4]), "=&v"(T[5]), "=&v"(T[6]), "=&v"(T[7]), "=&v"(T[8]),
-        "=&v"(T[9])
-      : "v"(U[1]), "v"(U[2]), "v"(U[3]), "v"(U[4]), "v"(U[5]), "v"(U[6]), "v"(U[7]), "v"(U[8]),
-        "v"(H[0]), "v"(H[1]), "v"(H[2]), "v"(H[3]), "v"(H[4]), "v"(H[5]), "v"(H[6]), "v"(H[7]), "v"(0u)
-      : "vcc");
-  fm_reduce_T(r, T, H);
-}
-
-FM_DEV void fm_reduce_T(Fe& r, const uint32_t T[10], const uint32_t* H) {
-  // P_i = 977*H_i + T_i  (< 2^42), independent
-  uint64_t P[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) P[i] = (uint64_t)H[i] * 977u + T[i];
-  // R = sum P_i 2^(32i) + (T9:T8) 2^256 : one carry chain; top = R9:R8 < 3 * 2^32
-  uint32_t R[8], R8, R9;
-  asm("v_mov_b32 %0, %10\n\t"
-      "v_add_co_u32_e32 %1, vcc, %11, %12\n\t"
+      "v_addc_co_u32_e32 %1, vcc, %11, %12, vcc\n\t"
       KHB_NOP
       "v_addc_co_u32_e32 %2, vcc, %13, %14, vcc\n\t"
       KHB_NOP
@@ -362,21 +299,64 @@ FM_DEV void fm_reduce_T(Fe& r, const uint32_t T[10], const uint32_t* H) {
       KHB_NOP
       "v_addc_co_u32_e32 %7, vcc, %23, %24, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, %25, %26, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %9, vcc, 0, %27, vcc"
-      : "=&v"(R[0]), "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]),
+      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
+      : "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]),
         "=&v"(R8), "=&v"(R9)
-      : "v"((uint32_t)P[0]),
-        "v"((uint32_t)P[1]), "v"((uint32_t)(P[0] >> 32)),
-        "v"((uint32_t)P[2]), "v"((uint32_t)(P[1] >> 32)),
-        "v"((uint32_t)P[3]), "v"((uint32_t)(P[2] >> 32)),
-        "v"((uint32_t)P[4]), "v"((uint32_t)(P[3] >> 32)),
-        "v"((uint32_t)P[5]), "v"((uint32_t)(P[4] >> 32)),
-        "v"((uint32_t)P[6]), "v"((uint32_t)(P[5] >> 32)),
-        "v"((uint32_t)P[7]), "v"((uint32_t)(P[6] >> 32)),
-        "v"(T[8]), "v"((uint32_t)(P[7] >> 32)), "v"(T[9])
+      : "v"((uint32_t)V[1]), "v"((uint32_t)(V[0] >> 32)),
+        "v"((uint32_t)V[2]), "v"((uint32_t)(V[1] >> 32)),
+        "v"((uint32_t)V[3]), "v"((uint32_t)(V[2] >> 32)),
+        "v"((uint32_t)V[4]), "v"((uint32_t)(V[3] >> 32)),
+        "v"((uint32_t)V[5]), "v"((uint32_t)(V[4] >> 32)),
+        "v"((uint32_t)V[6]), "v"((uint32_t)(V[5] >> 32)),
+        "v"((uint32_t)V[7]), "v"((uint32_t)(V[6] >> 32)),
+        "v"(T8), "v"((uint32_t)(V[7] >> 32)), "v"(0u)
       : "vcc");
+}
+
+// R9:R8:R[7..2] += sum_i ov_i 2^(32i) with ov_i the lane's bit of mask ov[i] (the carry out of V_i):
+// eight v_cndmask reading the SGPR masks, one carry chain.  S < 2^290, so nothing leaves R9.  The
+// masks were written by VALU (the mads) a whole R chain earlier; the leading pad keeps the distance
+// whatever is scheduled in between.
+FM_DEV void fm_fix_R(uint32_t R[8], uint32_t& R8, uint32_t& R9, const uint64_t ov[8]) {
+  uint32_t c[8];
+  asm("s_nop 1\n\t"
+      "v_cndmask_b32_e64 %8, 0, 1, %16\n\t"
+      "v_cndmask_b32_e64 %9, 0, 1, %17\n\t"
+      "v_cndmask_b32_e64 %10, 0, 1, %18\n\t"
+      "v_cndmask_b32_e64 %11, 0, 1, %19\n\t"
+      "v_cndmask_b32_e64 %12, 0, 1, %20\n\t"
+      "v_cndmask_b32_e64 %13, 0, 1, %21\n\t"
+      "v_cndmask_b32_e64 %14, 0, 1, %22\n\t"
+      "v_cndmask_b32_e64 %15, 0, 1, %23\n\t"
+      "v_add_co_u32_e32 %0, vcc, %0, %8\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %1, vcc, %1, %9, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %2, vcc, %2, %10, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %3, vcc, %3, %11, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %4, vcc, %4, %12, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %5, vcc, %5, %13, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %6, vcc, %6, %14, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %7, vcc, %7, %15, vcc"
+      : "+v"(R[2]), "+v"(R[3]), "+v"(R[4]), "+v"(R[5]), "+v"(R[6]), "+v"(R[7]), "+v"(R8), "+v"(R9),
+        "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]), "=&v"(c[4]), "=&v"(c[5]), "=&v"(c[6]), "=&v"(c[7])
+      : "s"(ov[0]), "s"(ov[1]), "s"(ov[2]), "s"(ov[3]), "s"(ov[4]), "s"(ov[5]), "s"(ov[6]), "s"(ov[7])
+      : "vcc");
+}
+
+// Lw + Lw8 2^256 + H (2^32 + 977) -> a value < 2^256 congruent to it (lazy).
+FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t* H) {
+  uint64_t V[8], ov[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) fm_madv(V[i], ov[i], H[i], Lw[i], 977u);
+  uint32_t R[8], R8, R9;              // top = R9:R8 < 3 * 2^32 once the carries are in
+  fm_chain_R(R, R8, R9, V, Lw8);
+  if (fm_any_mask(ov[0] | ov[1] | ov[2] | ov[3] | ov[4] | ov[5] | ov[6] | ov[7])) fm_fix_R(R, R8, R9, ov);
   // second fold: top = R9:R8 (< 3 * 2^32); add top*977 at limb 0 and top*2^32 at limb 1
   const uint64_t u = (uint64_t)R8 * 977u + (uint64_t)(R9 * 977u) * 0x100000000ull;   // < 2^44
   const uint64_t w = (uint64_t)(uint32_t)(u >> 32) + R8;                              // limb-1 addend
@@ -406,6 +386,42 @@ FM_DEV void fm_reduce_T(Fe& r, const uint32_t T[10], const uint32_t* H) {
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) r.v[i] = R[i];
+}
+
+// Reduce t (512 bits) mod p to a value < 2^256 (lazy).
+FM_DEV void fm_reduce(Fe& r, const uint32_t t[16]) { fm_reduce_V(r, t, 0u, t + 8); }
+
+// (t + w) mod p, lazy (< 2^256), for t a 512-bit product and any w < 2^256: the addend rides in
+// one carry chain U = L + w ahead of the V mads, so a following modular add/sub (x = s^2 - u)
+// costs 9 instructions instead of 19.  U + (H << 32) < 2^288 + 2^257, the bound R9:R8 < 3 * 2^32
+// relies on.
+FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
+  const uint32_t* L = t;
+  uint32_t U[9];
+  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
+      : "=&v"(U[0]), "=&v"(U[1]), "=&v"(U[2]), "=&v"(U[3]), "=&v"(U[4]), "=&v"(U[5]), "=&v"(U[6]), "=&v"(U[7]),
+        "=&v"(U[8])
+      : "v"(L[0]), "v"(L[1]), "v"(L[2]), "v"(L[3]), "v"(L[4]), "v"(L[5]), "v"(L[6]), "v"(L[7]),
+        "v"(w.v[0]), "v"(w.v[1]), "v"(w.v[2]), "v"(w.v[3]), "v"(w.v[4]), "v"(w.v[5]), "v"(w.v[6]), "v"(w.v[7]),
+        "v"(0u)
+      : "vcc");
+  fm_reduce_V(r, U, U[8], t + 8);
 }
 
 // Multiply / square: seeded columns (fm_mul512x / fm_sqr512x), then the reduction.  (The column-shuffle

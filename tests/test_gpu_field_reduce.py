@@ -1,0 +1,86 @@
+"""fm_mul / fm_sqr / fm_sqr_add (khb_field_op 0, 1, 6) on operands aimed at the carry-out of the reduction's V
+mads (tests/field_reduce.py): a carry in exactly one limb i for every i, in all limbs (products near p^2 and
+2^512, the addend 2^256 - 1), H_i on either side of the threshold, and a carry together with the second fold's
+c3 (ops 0 and 6) and with c3 and the wrap (op 6; op 1's combinations and op 0's wrap are not aimed at).  The
+canonical result equals the Python integer; the raw result (op | KHB_FIELD_OP_RAW) equals the limb model bit for bit, filler included.  The file is also meant for a
+KHB_RARE_FORCE build, where every wave takes the carry fix: tools/build_variant.sh with LIBDIR=1 and
+-DKHB_RARE_FORCE=1, then KHB_LIB_DIR=<that directory> pytest -m gpu on this file (profiles/r07_reduce/rare.txt)."""
+from __future__ import annotations
+
+import random
+
+import pytest
+
+from keyhuntm1cpu_amd.khbsgs import FIELD_OP_RAW as RAW
+from tests import adversarial as adv
+from tests import field_reduce as fr
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from keyhuntm1cpu_amd.khbsgs import Engine
+    e = Engine(0, lanes=16384)
+    yield e
+    e.close()
+
+
+def _be(vals) -> bytes:
+    return b"".join(v.to_bytes(32, "big") for v in vals)
+
+
+def _ints(raw: bytes) -> list:
+    return [int.from_bytes(raw[i:i + 32], "big") for i in range(0, len(raw), 32)]
+
+
+def _directed(op: int) -> list:
+    """Every class, 64 operands each, interleaved so that the fully directed wave holds all of them."""
+    classes = [fr.one_limb(op, i, 64, seed=3) for i in range(8)]
+    classes.append(fr.all_limbs(op, 64))
+    classes.append([e[:2] for e in fr.edge(op, 64, seed=3)])
+    if op == 0:
+        classes.append(fr.mul_with_c3(64, seed=3))
+    if op == 6:
+        classes.append(fr.with_second_fold("c3", 64, seed=3))
+        classes.append(fr.with_second_fold("wrap", 64, seed=3))
+    assert all(len(c) >= 64 for c in classes)
+    return [c[k] for k in range(64) for c in classes]
+
+
+def _batches(op: int, directed: list, rng: random.Random):
+    """Two batches with random filler.  The first (4,096 = 64 waves): wave 0 has all 64 lanes directed, waves
+    1..31 exactly one directed lane each, at a lane that moves from wave to wave, waves 32..63 none.  The second
+    (4,059: its last wave is partial) takes the rest at random places of its first 32 waves and one in its last
+    lane; the waves between hold none."""
+    first = [adv.random_operands(op, rng) for _ in range(4096)]
+    where1 = list(range(64)) + [64 * w + (7 * w + 3) % 64 for w in range(1, 32)]
+    for k, i in enumerate(where1):
+        first[i] = directed[k]
+    rest = directed[len(where1):]
+    assert 2 <= len(rest) <= 2048
+    n2 = 4096 - 37
+    second = [adv.random_operands(op, rng) for _ in range(n2)]
+    where2 = [n2 - 1] + rng.sample(range(2048), len(rest) - 1)
+    for k, i in enumerate(where2):
+        second[i] = rest[k]
+    return (first, set(where1)), (second, set(where2))
+
+
+@pytest.mark.parametrize("op", [0, 1, 6])
+def test_field_ops_carry_out(eng, op):
+    directed = _directed(op)
+    assert all(any(fr.expected_ov(op, a, b)) or (a, b) in [e[:2] for e in fr.edge(op, 64, seed=3)]
+               for a, b in directed)
+    rng = random.Random(60 + op)
+    for ops, where in _batches(op, directed, rng):
+        ab, bb = _be(a for a, _ in ops), _be(b for _, b in ops)
+        canon = _ints(eng.field_op(op, ab, bb))
+        raw = _ints(eng.field_op(op | RAW, ab, bb))
+        exact = [adv.EXACT[op](a, b) for a, b in ops]
+        model = [fr.v_op(op, a, b)[0] for a, b in ops]
+        assert model == [adv.MODEL[op](a, b)[0] for a, b in ops]
+        bad = [i for i in range(len(ops)) if canon[i] != exact[i]]
+        assert not bad, (op, "canonical", bad[:8], [i in where for i in bad[:8]])
+        bad = [i for i in range(len(ops)) if raw[i] != model[i]]
+        assert not bad, (op, "raw", bad[:8], [i in where for i in bad[:8]])

@@ -9,7 +9,9 @@ Inputs (all under profiles/):
   r06c/pmc_classes/        PMC instruction classes of one bench-sized product launch (SQ_INSTS_*)
   r06f/pmc_icache/         instruction fetches and I-cache misses of the same launch
   r05c/f64mul_time.jsonl   the field product's energy (fm_mul chains alone at full occupancy)
-  pmc_latest.json          VALU lane-instructions per giant step of the product
+  r06b/prof/pmc_latest.json  VALU lane-instructions per giant step of the round-6 kernel, the one every input above
+                           was measured on (profiles/pmc_latest.json follows the current kernel: 680.4 since the
+                           per-limb reduction, whose power and class counts have not been re-taken)
 Prints one JSON object; tests/test_measure_tools.py checks it against the figures DESIGN.md quotes.
 Usage: python tools/energy_split.py"""
 import collections
@@ -65,7 +67,7 @@ def main():
     fm_w = statistics.mean(r["power"]["power_w_from_energy"] for r in fm)
     fm_rate = statistics.mean(r["G_products_per_s"] for r in fm)
     pj_per_valu = (fm_w - sleep_w) / fm_rate / VALU_PER_FM_MUL * 1e3
-    with open(os.path.join(P, "pmc_latest.json")) as f:
+    with open(os.path.join(P, "r06b", "prof", "pmc_latest.json")) as f:
         valu = json.load(f)["valu_instr_per_giant_step"]
     cls = pmc_last(os.path.join(P, "r06c", "pmc_classes"))
     ic = pmc_last(os.path.join(P, "r06f", "pmc_icache"))
