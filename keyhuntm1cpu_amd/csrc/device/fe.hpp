@@ -31,6 +31,13 @@ struct Fe {
 #define KHB_P0 0xFFFFFC2Fu
 #define KHB_P1 0xFFFFFFFEu
 
+KHB_HD Fe fe_p() {
+  Fe p;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) p.v[k] = k == 0 ? KHB_P0 : (k == 1 ? KHB_P1 : 0xFFFFFFFFu);
+  return p;
+}
+
 KHB_HD void fe_set(Fe& r, const Fe& a) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) r.v[i] = a.v[i];

@@ -1,6 +1,6 @@
 // libkhbsgs.so — MI355X (gfx950) BSGS giant-step engine behind the C ABI of include/khbsgs.h:
 // contexts, submission slots, table loads, the self-test kernels and the launches of the
-// k_giant_scan instances (scan_kernels.hpp; instantiated in k_bsgs.hip, k_addr.hip, k_baby.hip).
+// k_giant_scan instances (scan_kernels.hpp + device/walk.hpp, scan_args.hpp; instantiated in k_bsgs/k_addr*/k_baby.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -279,7 +279,7 @@ uint64_t walked_groups(const Slot& S) {
   return v;
 }
 
-// Entries (32 B) of lane-private scratch: scan_group needs 512, scan_batch kBatch*514 + kBatch.
+// Entries (32 B) of lane-private scratch (device/walk.hpp): scan_group needs 512, scan_batch kBatch*514 + kBatch.
 constexpr size_t kScratchEntries = (size_t)kBatch * (kHalf + 3) > kHalf ? (size_t)kBatch * (kHalf + 3) : kHalf;
 
 void free_slot(Slot& S);

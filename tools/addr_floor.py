@@ -1,7 +1,8 @@
 """One -m address launch per library (config E: tests/unsolvedpuzzles.rmd, -l both by default, 8 chunks of
 2^32 keys from 2^70, the bench's launch) for PMC passes: rocprofv3 --pmc SQ_INSTS_VALU -- python3
 tools/addr_floor.py <lib.so>.  With the product library the counter gives the executed VALU per key;
-with the addrwalk build (tools/experiments/calib_build.sh addrwalk) it gives the x/y walk alone, the
+with an addrwalk build (the -m address kernels without the hashing; its patcher was removed in round 8, when it no
+longer applied, and git history has it) it gives the x/y walk alone, the
 walk term of the floor.  Prints one JSON line."""
 import json
 import os

@@ -39,7 +39,7 @@ def main():
     last = ""
     ops, cnd, seen = Counter(), [], 0
     prev = ""
-    movs, zero = Counter(), set()
+    movs, zero, inner = Counter(), set(), set()
 
     def track(s):
         """Keep `zero` (VGPRs known to hold 0) current over instruction s; classify s if it is a move."""
@@ -82,6 +82,10 @@ def main():
             tgt = s.split()[1]
             if labels[tgt] <= h:
                 break
+            if labels[tgt] <= i:          # an inner loop's back edge (a queue drain): one pass, then fall through
+                if tgt in inner:
+                    continue
+                inner.add(tgt)
             i = labels[tgt]
             continue
         if op.startswith("s_cbranch"):

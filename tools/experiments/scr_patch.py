@@ -2,7 +2,7 @@
 # index of the forward pass and the walk to (i & m), so the 16 B + 16 B per giant step of prefix
 # traffic stays in a few entries per group (MALL/L2-resident) instead of streaming through HBM.
 # Results are wrong by design (the walk reads the wrong prefixes).
-p = 'keyhuntm1cpu_amd/csrc/scan_kernels.hpp'
+p = 'keyhuntm1cpu_amd/csrc/device/walk.hpp'
 s = open(p).read()
 a = "pre = scr_ld(scr + (size_t)(i >= 2 ? i - 2 : 0) * S);"
 b = "pre = scr_ld(scr + (size_t)((i >= 2 ? i - 2 : 0) & KHB_SCR_MASK) * S);"

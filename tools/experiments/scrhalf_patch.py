@@ -7,14 +7,14 @@ import os
 import runpy
 here = os.path.dirname(os.path.abspath(__file__))
 runpy.run_path(os.path.join(here, "plainscr_patch.py"))
-p = 'keyhuntm1cpu_amd/csrc/scan_kernels.hpp'
+p = 'keyhuntm1cpu_amd/csrc/device/walk.hpp'
 s = open(p).read()
 a = "if (i > 2) pre = scr_ld(scr + (size_t)(i - 3) * S);"
 assert a in s
 s = s.replace(a, "if (i > 2) pre = scr_ld(scr + (size_t)((i - 3) & KHB_SCR_MASK) * S);")
-a = "Fe pre = scr_ld(scr + (size_t)(kHalf - 3) * S);          // P_509"
+a = "Fe pre = scr_ld(scr + (size_t)(HALF ? kHalf - 3 : kHalf - 2) * S);   // P_509 / P_510"
 assert a in s
-s = s.replace(a, "Fe pre = scr_ld(scr + (size_t)((kHalf - 3) & KHB_SCR_MASK) * S);")
+s = s.replace(a, "Fe pre = scr_ld(scr + (size_t)((HALF ? kHalf - 3 : kHalf - 2) & KHB_SCR_MASK) * S);")
 a = "if (!(kHalfStream && is_gated(MODE)) || (i & 1u)) scr_st(sg + i * S, a);"
 assert a in s
 s = s.replace(a, "if (!(kHalfStream && is_gated(MODE)) || (i & 1u)) scr_st(sg + (i & KHB_SCR_MASK) * S, a);")

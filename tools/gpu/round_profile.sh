@@ -7,7 +7,8 @@
 #      bench's auto 4096-chunk launch, so bench.py's roofline.traffic applies to its default line;
 #      FETCH_SIZE / WRITE_SIZE in passes of their own) and the SQ pass;
 #   3. config E: bench.py --workload address, and SQ_INSTS_VALU of one 8-chunk launch of the product
-#      library and of the hash-less addrwalk build (the x/y walk term of the floor, tools/addr_floor.py).
+#      library and, where a hash-less addrwalk build is present (its patcher went in round 8, when it no longer
+#      applied; git history has it), of that build (the x/y walk term of the floor, tools/addr_floor.py).
 # Usage: bash tools/gpu/round_profile.sh <tag> [steps]     Env: PARTS (default "trace pmc address"), PMC_JOBS
 # (chunks per PMC launch, default 4096 = the bench's auto batch at 4 waves/SIMD), K (default 1; K=4 PMC_JOBS=16384
 # PARTS=pmc gives config C's record, profiles/pmc_latest_k4.json).

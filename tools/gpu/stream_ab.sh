@@ -2,7 +2,8 @@
 # The prefix stream's cost, re-priced (round 5): product (non-temporal stream), plain-load/store stream, the stream
 # folded to 2 entries per group with non-temporal (scr2) and plain (scr2plain: L2-resident) accesses, and the half
 # stream; real gate, two launches in flight, board power.  Build: tools/experiments/calib_build.sh
-# plainscr|scr|half ... and the scr2plain pair (plainscr_patch + scr_patch), see DESIGN.md §5.
+# plainscr|scr|scrplain ..., and the half stream by tools/build_variant.sh half -DKHB_HALF_STREAM=1 (against a
+# -DKHB_HALF_STREAM=0 product: the half stream is the default since round 6), see DESIGN.md §5.
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/${1:-stream_ab}; mkdir -p $O
