@@ -3,6 +3,8 @@ from __future__ import annotations
 
 import random
 
+import numpy as np
+
 from oracle import ora
 
 P = ora.P
@@ -42,6 +44,22 @@ def gate_bits(lg: int, probes: int, x: int) -> list[int]:
 
 def gate_pass(gate: bytes, lg: int, probes: int, x: int) -> bool:
     return all((gate[b >> 3] >> (b & 7)) & 1 for b in gate_bits(lg, probes, x))
+
+
+def _popcount(b: bytes) -> int:
+    return int.from_bytes(b, "little").bit_count()
+
+
+def _fold(gate: bytes, log2_bytes: int) -> bytes:
+    """Block i of the fold = OR of the gate's 64-bit blocks j with j mod (2^log2_bytes / 8) == i."""
+    g = np.frombuffer(gate, dtype="<u8")
+    return np.bitwise_or.reduce(g.reshape(-1, (1 << log2_bytes) // 8), axis=0).tobytes()
+
+
+def _stage0(gate: bytes, log2_bytes: int) -> bytes:
+    """Word i = OR of the hi words of the gate's blocks j with j mod (2^log2_bytes / 4) == i."""
+    hi = np.frombuffer(gate, dtype="<u4")[1::2]
+    return np.bitwise_or.reduce(hi.reshape(-1, (1 << log2_bytes) // 4), axis=0).tobytes()
 
 
 def endo_planted_text(ora, picks, seed):

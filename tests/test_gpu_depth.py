@@ -153,6 +153,52 @@ def test_scan_refused_while_submission_pending():
     t.close()
 
 
+def test_scan_kinds_do_not_mix():
+    """With an -m address submission in flight khb_submit is refused (KHB_EBUSY) and khb_collect does not retire it
+    (KHB_ESTATE); khb_addr_collect then returns the hits of a plain khb_addr_scan of the same centre.  The mirror
+    image holds with a khb_submit in flight."""
+    import ctypes as C
+    import random
+    from keyhuntm1cpu_amd.khbsgs import AddrHit, Cand, Degenerate, Engine, Stats
+    EBUSY, ESTATE = -6, -5
+    t = khhost.Tables("0x100000000", 1, threads=8)
+    assert t.cycles == 64
+    tgt = khhost.pubkey(0x2000000000123457)
+    rng = random.Random(11)
+    abits = 1 << 16                                       # one bit in 16 set, two hashes: a few hundred hits
+    abf = bytes(sum(1 << k for k in range(8) if rng.random() < 1 / 16) for _ in range(abits // 8))
+    with Engine(0, lanes=16384) as e:
+        bf, nb, bits, h = t.bloom_concat(1)
+        e.load_bloom(bf, nb, bits, h)
+        e.load_addr_bloom(abf, abits, 2)
+        e.load_giant_table(t.giant_table())
+        offs, gpl = t.lane_offsets()
+        e.load_lane_offsets(offs, gpl)
+        c0 = t.chunk_centre(0x2000000000000000, tgt)
+        ref_hits, _ = e.addr_scan(c0, 0, t.cycles)
+        ref_cands, _, _ = e.scan(c0, 0, t.cycles)
+        assert len(ref_hits) > 50 and ref_cands
+        cap = 1 << 16
+        hits, cand, deg, st = (AddrHit * cap)(), (Cand * cap)(), (Degenerate * 64)(), Stats()
+        L, steps = e.L, t.cycles * 1024
+
+        assert L.khb_addr_submit(e.h, c0, 1, 0, t.cycles, 2) == 0
+        assert L.khb_submit(e.h, c0, 1, 0, t.cycles) == EBUSY
+        assert L.khb_collect(e.h, cand, cap, deg, 64, C.byref(st)) == ESTATE
+        assert L.khb_addr_collect(e.h, hits, cap, C.byref(st)) == 0
+        assert st.giant_steps == steps and st.n_cand == len(ref_hits)
+        got = [(int(x.job), int(x.group), int(x.t), int(x.kind)) for x in hits[:st.n_cand]]
+        assert sorted(got) == sorted(ref_hits)
+
+        assert L.khb_submit(e.h, c0, 1, 0, t.cycles) == 0
+        assert L.khb_addr_submit(e.h, c0, 1, 0, t.cycles, 2) == EBUSY
+        assert L.khb_addr_collect(e.h, hits, cap, C.byref(st)) == ESTATE
+        assert L.khb_collect(e.h, cand, cap, deg, 64, C.byref(st)) == 0
+        assert st.giant_steps == steps and st.n_cand == len(ref_cands) and st.n_degenerate == 0
+        assert sorted((int(x.job), int(x.a)) for x in cand[:st.n_cand]) == sorted(ref_cands)
+    t.close()
+
+
 def _one_slot_lanes() -> int:
     """Lanes whose scratch (kBatch x 515 entries of 32 B per lane) takes 60 % of the device's HBM: one
     submission slot fits, a second cannot."""

@@ -19,29 +19,13 @@ import pytest
 from keyhuntm1cpu_amd import BIN_DIR, khhost
 from keyhuntm1cpu_amd.khbsgs import Engine
 from keyhuntm1cpu_amd.khhost import TABLE_FOLD, TABLE_GATE, TABLE_L1, TABLE_STAGE0
-from tests.helpers import gate_bits
+from tests.helpers import _fold, _popcount, _stage0, gate_bits
 
 pytestmark = pytest.mark.gpu
 LANES = 64 * 256
 P63 = "0365ec2994b8cc0a20d40dd69edfe55ca32a54bcbbaa6b0ddcff36049301a54579"
 P125 = "0233709eb11e0d4439a729f21c2c443dedb727528229713f0065721ba8fa46f00e"
 GIB = 1 << 30
-
-
-def _popcount(b: bytes) -> int:
-    return int.from_bytes(b, "little").bit_count()
-
-
-def _fold(gate: bytes, log2_bytes: int) -> bytes:
-    """Block i of the fold = OR of the gate's 64-bit blocks j with j mod (2^log2_bytes / 8) == i."""
-    g = np.frombuffer(gate, dtype="<u8")
-    return np.bitwise_or.reduce(g.reshape(-1, (1 << log2_bytes) // 8), axis=0).tobytes()
-
-
-def _stage0(gate: bytes, log2_bytes: int) -> bytes:
-    """Word i = OR of the hi words of the gate's blocks j with j mod (2^log2_bytes / 4) == i."""
-    hi = np.frombuffer(gate, dtype="<u4")[1::2]
-    return np.bitwise_or.reduce(hi.reshape(-1, (1 << log2_bytes) // 4), axis=0).tobytes()
 
 
 # ---------------------------------------------------------------------------------- 1. byte parity

@@ -8,7 +8,7 @@ import random
 
 import pytest
 
-from tests.helpers import P, gate_pass, lane_offsets, rand_fe
+from tests.helpers import P, _fold, _popcount, _stage0, gate_pass, lane_offsets, rand_fe
 
 pytestmark = pytest.mark.gpu
 
@@ -237,6 +237,12 @@ def _l1_check(bf: bytes, nb: int, bits: int, hashes: int, xb: bytes, ora) -> boo
     return True
 
 
+def _random_gate(rng: random.Random, lg: int, probes: int) -> bytes:
+    """2^lg bits, each set with p = 0.5^(1/probes): about half of all x pass."""
+    fill = 0.5 ** (1.0 / probes)
+    return bytes(sum(1 << k for k in range(8) if rng.random() < fill) for _ in range((1 << lg) // 8))
+
+
 @pytest.mark.parametrize("probes", [1, 2, 3])
 def test_gate_candidates_exact(eng, bs32, ora, probes):
     """Level-0 gate (khb_load_gate): the candidates are exactly the giant steps whose x passes the
@@ -252,8 +258,7 @@ def test_gate_candidates_exact(eng, bs32, ora, probes):
     bf = bytes(sum(1 << k for k in range(8) if rng.random() < 0.97) for _ in range(256 * nb))
     eng.load_bloom(bf, nb, bits, hashes)
     lg = 16
-    fill = 0.5 ** (1.0 / probes)
-    gate = bytes(sum(1 << k for k in range(8) if rng.random() < fill) for _ in range((1 << lg) // 8))
+    gate = _random_gate(rng, lg, probes)
     centres, l1_ref, gate_ref = [], [], []
     for c in range(4):
         st = bs32.chunk_start(0x3000000000000000 + c * (1 << 33), ora.pubkey(0xABCDEF0123 + c))
@@ -292,3 +297,45 @@ def test_gate_candidates_exact(eng, bs32, ora, probes):
         eng.set_gate_stage0(0)                 # the library default: no stage 0
         eng.load_gate(None)
         load_tables(eng, bs32, gpl)
+
+
+@pytest.mark.parametrize("lg,stage1,stage0", [(16, 12, 10), (20, 11, 10)])
+@pytest.mark.parametrize("probes", [1, 2, 3])
+def test_loaded_gate_stages_byte_exact(eng, lg, stage1, stage0, probes):
+    """What khb_load_gate leaves on the device, byte for byte: the gate as given (with one probe, every block's hi
+    word set), its stage-1 fold (2^16 bits folded to 4 KiB: two gate blocks per fold block; 2^20 bits to 2 KiB: 64)
+    and, for two or more probes, the stage-0 filter of the hi words; the device popcounts agree, and gate_probe
+    gives the gate's own answer with both stages supersets of it."""
+    from keyhuntm1cpu_amd.khhost import TABLE_FOLD, TABLE_GATE, TABLE_STAGE0
+    rng = random.Random(7)
+    gate = _random_gate(rng, lg, probes)
+    xs = [rng.randrange(1, 1 << 256) for _ in range(256)]
+    try:
+        eng.set_gate_stage1(stage1)
+        eng.set_gate_stage0(stage0)
+        eng.load_gate(gate, lg, probes)
+        want = gate
+        if probes == 1:
+            want = b"".join(gate[i:i + 4] + b"\xff\xff\xff\xff" for i in range(0, len(gate), 8))
+        got = eng.resident_read(TABLE_GATE)
+        assert got == want
+        fold = _fold(got, stage1)
+        assert eng.resident_bytes(TABLE_FOLD) == 1 << stage1
+        assert eng.resident_read(TABLE_FOLD) == fold
+        assert eng.resident_popcount(TABLE_GATE) == _popcount(got)
+        assert eng.resident_popcount(TABLE_FOLD) == _popcount(fold)
+        if probes >= 2:
+            z = _stage0(got, stage0)
+            assert eng.resident_bytes(TABLE_STAGE0) == 1 << stage0
+            assert eng.resident_read(TABLE_STAGE0) == z
+            assert eng.resident_popcount(TABLE_STAGE0) == _popcount(z)
+        else:
+            assert eng.resident_bytes(TABLE_STAGE0) == 0
+        bits = eng.gate_probe(b"".join(x.to_bytes(32, "big") for x in xs))
+        assert [bool(v & 1) for v in bits] == [gate_pass(gate, lg, probes, x) for x in xs]
+        assert any(v & 1 for v in bits) and not all(v & 1 for v in bits)
+        assert all((v & 6) == 6 for v in bits if v & 1)         # the stages are supersets of the gate
+    finally:
+        eng.set_gate_stage1(1)                 # KHB_GATE_STAGE1_AUTO, the library default
+        eng.set_gate_stage0(0)                 # the library default: no stage 0
+        eng.load_gate(None)
