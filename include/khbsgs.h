@@ -52,7 +52,9 @@ extern "C" {
  * (khb_build_l1_resident, khb_mem_info, khb_resident_bytes / khb_resident_read / khb_resident_popcount and
  * khb_gate_probe) are additions to ABI 7: no existing signature or struct changed, so the version stays 7 (a bench
  * line's build record, which tests/test_launch.py pins to "7", keeps naming the same scan ABI); a caller that needs
- * them checks for the khb_build_l1_resident symbol. */
+ * them checks for the khb_build_l1_resident symbol.  -m address -c eth (KHB_SEARCH_ETH, KHB_ADDR_KIND_ETH and
+ * khb_hash160 kind 3) is an addition of the same sort: new values of existing arguments, version 7; a caller that
+ * needs it checks for KHB_SEARCH_ETH in this header, and a library without it answers KHB_EINVAL. */
 #define KHB_ABI_VERSION 7
 int khb_abi_version(void);
 /* What this library was built as, one line of `key=value` words: abi, arch, variant ("product" for the in-tree
@@ -260,7 +262,7 @@ int khb_field_op(khb_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8
 /* Bloom self-test kernel: hit[i] = bloom_check(level-1, x[i]) for 32-byte BE x values. */
 int khb_probe(khb_ctx* ctx, const uint8_t* xs, uint8_t* hit, uint32_t n);
 
-/* ---- -m address / -m rmd160 (keyhunt.cpp:2586-2937, BTC P2PKH, with or without -e) ----
+/* ---- -m address / -m rmd160 (keyhunt.cpp:2586-3002: BTC P2PKH, with or without -e, and -c eth) ----
  * The same group walk with the table Gn[i] = (i+1)*stride*G, _2Gn = 1024*stride*G loaded through
  * khb_load_giant_table (init_generator, keyhunt.cpp:4386-4399), lane offsets as above.  A job is
  * one claimed chunk; centres[k] = pubkey(chunk_base_k + 512*stride) (keyhunt.cpp:2587-2589), so
@@ -272,11 +274,13 @@ typedef struct {
   uint32_t kind;     /* form | e << 2.  form: 0 = compressed prefix 02, 1 = compressed prefix 03, 2 = uncompressed
                         (x, y), 3 = uncompressed (x, p - y), the negated point (-e only).  e: the point itself (0),
                         or with -e (beta*x, y) = lambda*P (1) and (beta^2*x, y) = lambda^2*P (2), keyhunt.cpp:2646-2763.
-                        Without -e kind is 0, 1 or 2 as before. */
+                        Without -e kind is 0, 1 or 2 as before.  KHB_ADDR_KIND_ETH: the ETH address of the point
+                        (KHB_SEARCH_ETH). */
 } khb_addr_hit;
+#define KHB_ADDR_KIND_ETH 16   /* disjoint from form | e << 2 (at most 11) */
 
-/* The single target bloom of -m address (bloom over 20-byte hash160 values, initBloomFilter,
- * keyhunt.cpp:6559-6576). */
+/* The single target bloom of -m address (bloom over 20-byte values, hash160s or with -c eth addresses,
+ * initBloomFilter, keyhunt.cpp:6559-6576). */
 int khb_load_addr_bloom(khb_ctx* ctx, const uint8_t* bf, uint64_t bytes, uint64_t bits, uint32_t hashes);
 /* search: 0 = uncompress, 1 = compress, 2 = both (keyhunt.cpp:59-61, -l), optionally OR'ed with
  * KHB_SEARCH_ENDOMORPHISM (-e, keyhunt.cpp:579-585, 2646-2763): per point also beta*x and beta^2*x (compressed:
@@ -284,8 +288,14 @@ int khb_load_addr_bloom(khb_ctx* ctx, const uint8_t* bf, uint64_t bytes, uint64_
  * hash160(s) are probed in the bloom; bloom hits are returned (the host runs searchbinary and the key
  * recovery: lambda^e * key, negated as the hit's form says).  group_begin must be a multiple of groups_per_lane.
  * Submissions share the context's two slots with khb_submit (two in flight, FIFO collect, a third returns
- * KHB_EBUSY). */
+ * KHB_EBUSY).
+ * search == KHB_SEARCH_ETH (-c eth, keyhunt.cpp:2776-2780, 2989-3002): per point one Keccak-256 of x || y, bytes
+ * 12..31 of the digest probed in the bloom; hits have kind KHB_ADDR_KIND_ETH and the host confirms them with the
+ * point's own key.  Exactly that value: combined with KHB_SEARCH_ENDOMORPHISM or with -l bits it is KHB_EINVAL
+ * (the reference's -c eth -e hashes beta*x twice where beta^2*x was meant, keyhunt.cpp:2772, and can report a
+ * key that does not own the address; it is not reproduced). */
 #define KHB_SEARCH_ENDOMORPHISM 4
+#define KHB_SEARCH_ETH 8
 int khb_addr_submit(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, uint32_t group_begin,
                     uint32_t group_count, int search);
 /* stats->n_cand = number of bloom hits (may exceed cap); giant_steps = keys scanned. */
@@ -295,8 +305,9 @@ int khb_addr_scan(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, u
 /* parity: x||y (64 bytes BE per point, t = 0..1023 per group) of ONE job. */
 int khb_addr_dump(khb_ctx* ctx, const uint8_t* centre_xy_be, uint32_t group_begin, uint32_t group_count,
                   uint8_t* xy);
-/* self-test: out[21*i] = hash160 (20 bytes) of point i (x||y BE) for kind 0/1/2, then one byte =
- * bloom_check20 result against the loaded address bloom (0 when none is loaded). */
+/* self-test: out[21*i] = hash160 (20 bytes) of point i (x||y BE) for kind 0/1/2, or its ETH address for kind 3
+ * (any 64 bytes: the hash does not need a point of the curve), then one byte = bloom_check20 result against the
+ * loaded address bloom (0 when none is loaded). */
 int khb_hash160(khb_ctx* ctx, int kind, const uint8_t* xy_be, uint8_t* out, uint32_t n);
 
 /* ---- baby-step tables on the GPU (thread_bPload, keyhunt.cpp:4404-4592; orchestration 1615-1880) ----

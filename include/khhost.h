@@ -19,8 +19,10 @@ extern "C" {
 
 /* ABI version of this header; bumped whenever a signature, a struct or an output array changes.
  * A binding checks khh_abi_version() == the KHH_ABI_VERSION it was written for before any other call.
- * ABI 7 added resident tables (large -k): khh_tables_new_resident and the khh_session_resident_* calls. */
-#define KHH_ABI_VERSION 7
+ * ABI 7 added resident tables (large -k): khh_tables_new_resident and the khh_session_resident_* calls.
+ * ABI 8 added -m address -c eth: khh_addr_new_eth, khh_addr_skipped, khh_eth_address, search = KHB_SEARCH_ETH and
+ * khh_addr_confirm's kind KHB_ADDR_KIND_ETH. */
+#define KHH_ABI_VERSION 8
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -156,20 +158,31 @@ uint64_t khh_session_recorded(const khh_session* s, uint8_t* bases_be, uint32_t*
 int khh_pubkey(const uint8_t key_be[32], uint8_t out_xy[64]);
 int khh_parse_pubkey(const char* hex, uint8_t out_xy[64], int* compressed);
 
-/* ---- -m address / -m rmd160 (BTC P2PKH) ----
+/* ---- -m address / -m rmd160 (BTC P2PKH, and ETH addresses with -c eth) ----
  * Targets from a target file's text (base58 addresses or 40-hex rmd160 lines, keyhunt.cpp:6300-6358).
  * The generator (Gn table + lane offsets for chunks of n_seq keys) is built for stride and gpl. */
 typedef struct khh_addr khh_addr;
 khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                        uint32_t gpl, int threads, char* err, size_t errlen);
+/* -c eth: targets as forceReadFileAddressEth reads them (keyhunt.cpp:6374-6450).  Lines are trimmed of " \t\n\r";
+ * lines of 40 or more characters size the bloom; a 40-character line must be hex, a 42-character line hex from
+ * its third character (the two leading characters are not looked at), either letter case; every other counted
+ * line is skipped.  Such a handle is searched with KHB_SEARCH_ETH only, and a khh_addr_new handle never with it:
+ * the mismatch is an error return with a message, not an empty search. */
+khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
+                           uint32_t gpl, int threads, char* err, size_t errlen);
 void khh_addr_free(khh_addr* a);
+/* lines the loader omitted ("[I] Ommiting invalid line") */
+uint64_t khh_addr_skipped(const khh_addr* a);
 /* sorted 20-byte table (n entries) and the target bloom */
 const uint8_t* khh_addr_table(const khh_addr* a, uint64_t* n);
 const uint8_t* khh_addr_bloom(const khh_addr* a, uint64_t* bytes, uint64_t* bits, uint32_t* hashes);
 void khh_addr_giant_table(const khh_addr* a, uint8_t out[513 * 64]);
 uint32_t khh_addr_lane_offsets(const khh_addr* a, uint8_t* out /* n*64, may be NULL */, uint32_t* gpl);
 /* Sequential (random_chunks = 0) or -R search of [start, end) with search 0/1/2 (-l), OR'ed with
- * KHB_SEARCH_ENDOMORPHISM (4, include/khbsgs.h) for -e: the found keys are then lambda^e multiples too.  Found keys
+ * KHB_SEARCH_ENDOMORPHISM (4, include/khbsgs.h) for -e: the found keys are then lambda^e multiples too; or with
+ * search = KHB_SEARCH_ETH (8) alone on a khh_addr_new_eth handle: found keys come back with compressed = 0 and the
+ * 20 address bytes in rmd.  Found keys
  * (32 B BE each) with compressed flags and rmd160s, in discovery order; *n_found may exceed cap.
  * Discovery order is batch order, and (chunk, key) order inside a batch, except after an overflow: a batch
  * whose bloom hits overflowed khb_addr_hit_capacity is rescanned in parts queued behind the batch already
@@ -193,12 +206,15 @@ int khh_addr_set_hit_capacity(khh_addr* a, uint32_t cap);
 /* The host confirmation of one GPU bloom hit (khb_addr_hit.kind = form | e << 2) of the point with key key_be:
  * searchbinary of the hash the kind names, then the reference's key recovery (keyhunt.cpp:2789-2937; lambda^e * key,
  * negated for the other point of a compressed x or for form 3).  Returns 1 and the key / compressed flag when the
- * hash is a target, 0 when it is not. */
+ * hash is a target, 0 when it is not.  kind KHB_ADDR_KIND_ETH (keyhunt.cpp:2989-3002): the ETH address of key*G
+ * is looked up and the key returned unchanged. */
 int khh_addr_confirm(const khh_addr* a, const uint8_t key_be[32], uint32_t kind, uint8_t out_key_be[32],
                      int* compressed);
 /* hash160 of a public key (x||y BE) and its P2PKH address (out_addr >= 36 bytes) */
 void khh_hash160(const uint8_t xy[64], int compressed, uint8_t out[20]);
 void khh_rmd_to_address(const uint8_t rmd[20], char* out_addr);
+/* ETH address of a public key (x||y BE; any 64 bytes): bytes 12..31 of Keccak-256(x||y), keyhunt.cpp:4783-4789 */
+void khh_eth_address(const uint8_t xy[64], uint8_t out[20]);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,9 @@
-// -m address / -m rmd160: what the x,y walk does with each point (hash160 + the target bloom, or the x||y dump).
+// -m address / -m rmd160: what the x,y walk does with each point (hash160 or, with -c eth, the ETH address + the
+// target bloom, or the x||y dump).
 #pragma once
 #include "scan_args.hpp"
 #include "hash160.hpp"
+#include "keccak.hpp"
 
 namespace khbk {
 
@@ -17,6 +19,12 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
     uint8_t* o = A.xdump + ((uint64_t)(j - A.group_begin) * KHB_GROUP + t) * 64;
     fe_to_be(o, x);
     fe_to_be(o + 32, y);
+  } else if constexpr (MODE == kAddrEth) {
+    // -c eth (keyhunt.cpp:2776-2780, 2989-3002): one Keccak-f[1600] per point; the address words are already in
+    // bloom_check20's byte order
+    uint32_t h[5];
+    eth_address(h, x, y);
+    if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, KHB_ADDR_KIND_ETH);
   } else {
     uint32_t h[5];
     if constexpr (is_endo(MODE)) {

@@ -48,6 +48,7 @@ KHB_HD uint32_t bitop3(uint32_t x, uint32_t y, uint32_t z) {
 #endif
 }
 KHB_HD uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) { return bitop3<0x96u>(x, y, z); }
+KHB_HD uint32_t chi3(uint32_t x, uint32_t y, uint32_t z) { return bitop3<0xD2u>(x, y, z); }   // x ^ (~y & z): Keccak's chi
 
 // ---- SHA-256 (FIPS 180-4 §6.2) ----
 #define KHB_SHA_K                                                                                            \

@@ -64,14 +64,17 @@ enum : int {
   kAddrUE = 10,    // kAddrU / kAddrC / kAddrB with -e (KHB_SEARCH_ENDOMORPHISM: beta*x, beta^2*x, negated y;
   kAddrCE = 11,    //   keyhunt.cpp:2646-2763)
   kAddrBE = 12,
+  kAddrEth = 13,   // -m address -c eth: Keccak-256 of x || y (keyhunt.cpp:2776-2780; device/keccak.hpp)
 };
 constexpr bool is_gated(int m) { return m == kScanG || m == kScanG1 || m == kScanG2; }
 // filter stages in front of the full gate: 0 (kScanG), 1 (the fold, kScanG1), 2 (filter + fold, kScanG2)
 constexpr int gate_stages(int m) { return m == kScanG2 ? 2 : m == kScanG1 ? 1 : 0; }
 constexpr bool is_scan(int m) { return m == kScan || is_gated(m); }
 constexpr bool is_endo(int m) { return m >= kAddrUE && m <= kAddrBE; }
-constexpr bool is_addr(int m) { return (m >= kAddrU && m <= kAddrDump) || is_endo(m); }
-constexpr bool needs_y(int m) { return m == kAddrU || m == kAddrB || m == kAddrDump || m == kAddrUE || m == kAddrBE; }
+constexpr bool is_addr(int m) { return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth; }
+constexpr bool needs_y(int m) {
+  return m == kAddrU || m == kAddrB || m == kAddrDump || m == kAddrUE || m == kAddrBE || m == kAddrEth;
+}
 constexpr bool addr_compressed(int m) { return m == kAddrC || m == kAddrB || m == kAddrCE || m == kAddrBE; }
 constexpr bool addr_uncompressed(int m) { return m == kAddrU || m == kAddrB || m == kAddrUE || m == kAddrBE; }
 constexpr bool is_dump(int m) { return m == kDump || m == kAddrDump || m == kBaby; }
@@ -83,8 +86,16 @@ constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and
 #ifndef KHB_ADDR_E_WAVES_PER_SIMD
 #define KHB_ADDR_E_WAVES_PER_SIMD KHB_ADDR_WAVES_PER_SIMD   // occupancy target of the -e address kernels
 #endif
+#ifndef KHB_ADDR_ETH_WAVES_PER_SIMD
+// occupancy target of the -c eth kernel: 3 waves (168 VGPRs, no scratch) with the rolled Keccak measured 2.4 % less
+// kernel time than 4 (128 VGPRs, 208 B of scratch) and 27 % less than 2 (profiles/eth)
+#define KHB_ADDR_ETH_WAVES_PER_SIMD 3
+#endif
 constexpr int waves_per_simd(int m) {
-  return is_endo(m) ? KHB_ADDR_E_WAVES_PER_SIMD : is_addr(m) ? KHB_ADDR_WAVES_PER_SIMD : KHB_WAVES_PER_SIMD;
+  return m == kAddrEth ? KHB_ADDR_ETH_WAVES_PER_SIMD
+         : is_endo(m)  ? KHB_ADDR_E_WAVES_PER_SIMD
+         : is_addr(m)  ? KHB_ADDR_WAVES_PER_SIMD
+                       : KHB_WAVES_PER_SIMD;
 }
 constexpr uint32_t kHalf = KHB_GROUP / 2;            // 512
 constexpr uint32_t kCandCap = 1u << 20;

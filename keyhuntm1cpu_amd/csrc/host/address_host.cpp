@@ -11,6 +11,7 @@
 
 #include "../../../include/khbsgs.h"
 #include "../device/hash160.hpp"
+#include "../device/keccak.hpp"
 
 namespace khb {
 
@@ -74,6 +75,21 @@ void hash160_x(uint8_t prefix, const Pt& p, uint8_t out[20]) {
   uint32_t h[5];
   hash160_compressed(h, prefix, x);
   bytes_of_words(out, h);
+}
+
+void eth_address_xy(const uint8_t xy[64], uint8_t out[20]) {
+  Fe x, y;
+  fe_from_be(x, xy);
+  fe_from_be(y, xy + 32);
+  uint32_t h[5];
+  eth_address(h, x, y);
+  bytes_of_words(out, h);
+}
+
+void eth_address_pub(const Pt& p, uint8_t out[20]) {
+  uint8_t b[64];
+  pt_to_be(b, p);
+  eth_address_xy(b, out);
 }
 
 // -------------------------------------------------------------------------------- base58
@@ -225,7 +241,48 @@ bool AddrTargets::load_text(const std::string& text, int bloom_multiplier, AddrT
   return true;
 }
 
-bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err) {
+// forceReadFileAddressEth (keyhunt.cpp:6374-6450): lines of 40 or more characters size the bloom; a 40-character
+// line must be hex, a 42-character line hex from its third character (the two leading characters are not looked
+// at); hexs2bin takes either letter case.
+bool AddrTargets::load_text_eth(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err) {
+  T = AddrTargets();
+  T.eth = true;
+  const std::vector<std::string> lines = fgets_lines(text);
+  char aux[128];
+  for (const std::string& l : lines) {
+    snprintf(aux, sizeof aux, "%s", l.c_str());
+    trim(aux);
+    if (strlen(aux) >= 40) ++T.counted;
+  }
+  const uint64_t entries = T.counted <= 10000 ? 10000 : (uint64_t)(bloom_multiplier > 0 ? bloom_multiplier : 1) * T.counted;
+  if (T.bloom.init2(entries, 0.000001L) != 0) {
+    if (err) *err = "bloom_init failed";
+    return false;
+  }
+  uint64_t items = T.counted, i = 0;
+  size_t li = 0;
+  while (i < items && li < lines.size()) {
+    snprintf(aux, sizeof aux, "%s", lines[li++].c_str());
+    trim(aux);
+    const size_t r = strlen(aux);
+    const char* hex = r == 40 ? aux : r == 42 ? aux + 2 : nullptr;
+    if (hex && all_hex(hex)) {
+      H160 h;
+      for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(hex[2 * k]) * 16 + hexv(hex[2 * k + 1]));
+      T.bloom.add20(h.data());
+      T.table.push_back(h);
+      ++i;
+    } else {
+      T.skipped.push_back(aux);
+      --items;
+    }
+  }
+  std::sort(T.table.begin(), T.table.end(),
+            [](const H160& a, const H160& b) { return memcmp(a.data(), b.data(), 20) < 0; });
+  return true;
+}
+
+bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err, bool eth) {
   FILE* f = fopen(path, "r");
   if (!f) {
     if (err) *err = std::string("Error opening the file ") + path;
@@ -236,7 +293,7 @@ bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets&
   size_t n;
   while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
   fclose(f);
-  return load_text(text, bloom_multiplier, T, err);
+  return eth ? load_text_eth(text, bloom_multiplier, T, err) : load_text(text, bloom_multiplier, T, err);
 }
 
 bool AddrTargets::searchbinary(const uint8_t data[20]) const {
@@ -309,6 +366,20 @@ const U256& endo_lambda(int e) {
 // the reference decides by the parity of y, 2800-2860, which gives the same key).  Uncompressed form 2 is k' itself,
 // form 3 (-e only) the negated point, n - k' (keyhunt.cpp:2876-2920).
 bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound* out) {
+  if (kind == KHB_ADDR_KIND_ETH) {
+    // -c eth (keyhunt.cpp:2989-3002): the address of key*G itself; the reported key is the scanned key, never negated
+    U256 k;
+    U256::divmod(key, secp_order(), nullptr, &k);
+    if (!T.eth || k.is_zero()) return false;
+    uint8_t h[20];
+    eth_address_pub(mul_g(k), h);
+    if (!T.searchbinary(h)) return false;
+    out->key = key;
+    out->compressed = false;
+    memcpy(out->rmd.data(), h, 20);
+    return true;
+  }
+  if (T.eth) return false;
   const uint32_t form = kind & 3u, e = kind >> 2;
   if (e > 2) return false;
   U256 k;
@@ -561,6 +632,14 @@ int addr_search(const AddrTargets& T, const AddrGen& G, const AddrConfig& cfg, c
   if (cfg.n_seq < 1024 || cfg.n_seq % 1024 || cfg.n_seq / 1024 > 0xFFFFFFFFull) {
     if (err) *err = "n must be a positive multiple of 1024";
     return -100;
+  }
+  const bool eth = cfg.search == KHB_SEARCH_ETH;
+  if (eth != T.eth || (eth && cfg.endomorphism) || (!eth && (cfg.search < 0 || cfg.search > 2))) {
+    if (err)
+      *err = T.eth ? "targets loaded for -c eth are searched with KHB_SEARCH_ETH alone (no -l bits, no -e)"
+                   : eth ? "KHB_SEARCH_ETH needs targets loaded for -c eth (these are BTC hash160 targets)"
+                         : "search must be 0, 1 or 2 (-l), optionally with -e";
+    return KHB_EINVAL;
   }
   if ((cfg.n_seq / 1024 + G.gpl - 1) / G.gpl > G.offs.size()) {
     if (err) *err = "generator lane offsets do not cover a chunk";

@@ -1,5 +1,5 @@
-// Host side of keyhunt's -m address / -m rmd160 modes (BTC P2PKH, with or without -e) on libkhbsgs:
-// target loading (forceReadFileAddress, keyhunt.cpp:6300-6358), the generator table
+// Host side of keyhunt's -m address / -m rmd160 modes (BTC P2PKH, with or without -e; -c eth) on libkhbsgs:
+// target loading (forceReadFileAddress, keyhunt.cpp:6300-6358; forceReadFileAddressEth, 6374-6450), the generator table
 // (init_generator, keyhunt.cpp:4386-4399), chunk claiming (thread_process, keyhunt.cpp:2546-2567),
 // and the confirmation of GPU bloom hits (searchbinary + key recovery, keyhunt.cpp:2789-2937).
 #pragma once
@@ -26,16 +26,23 @@ void sha256(const uint8_t* msg, size_t len, uint8_t out[32]);
 // GetHash160(P2PKH, compressed, P) (SECP256K1.cpp:671-705) / GetHash160_fromX (:707-789)
 void hash160_pub(const Pt& p, bool compressed, uint8_t out[20]);
 void hash160_x(uint8_t prefix, const Pt& p, uint8_t out[20]);
+// generate_binaddress_eth (keyhunt.cpp:4783-4789): bytes 12..31 of Keccak-256(x || y)
+void eth_address_xy(const uint8_t xy[64], uint8_t out[20]);
+void eth_address_pub(const Pt& p, uint8_t out[20]);
 
 struct AddrTargets {
   std::vector<H160> table;             // sorted (memcmp), the reference's addressTable after _sort
   BloomFilter bloom;                   // initBloomFilter(counted lines)
   uint64_t counted = 0;                // lines longer than 20 characters (sizes the bloom)
   std::vector<std::string> skipped;    // "[I] Ommiting invalid line"
+  bool eth = false;                    // -c eth: the table holds ETH addresses (load_text_eth)
 
   // text: the target file's contents.  Returns false with *err on an unusable bloom.
   static bool load_text(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
-  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err);
+  // -c eth: 40-hex lines, with or without a two-character prefix (forceReadFileAddressEth); counted = lines of
+  // 40 or more characters
+  static bool load_text_eth(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
+  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err, bool eth = false);
   bool searchbinary(const uint8_t h[20]) const;   // keyhunt.cpp:2311-2335, literal
 };
 
@@ -50,7 +57,8 @@ struct AddrGen {
 };
 
 struct AddrConfig {
-  int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300)
+  int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300), or
+                                       // KHB_SEARCH_ETH (-c eth; the targets must be load_text_eth's)
   bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and negated points
   U256 start{1}, end{1};               // [start, end): n_range_start / n_range_end
   uint64_t n_seq = 1ull << 32;         // keys per claimed chunk (-n, N_SEQUENTIAL_MAX)
@@ -65,7 +73,7 @@ struct AddrConfig {
 struct AddrFound {
   U256 key;
   bool compressed;
-  H160 rmd;
+  H160 rmd;                            // the hash160, or the ETH address (-c eth)
 };
 
 struct AddrStats {
@@ -86,6 +94,7 @@ struct AddrCallbacks {
 // Confirm one GPU bloom hit (khb_addr_hit.kind = form | e << 2) of the point whose key is `key`: searchbinary of the
 // hash the kind names, then the reference's key recovery (keyhunt.cpp:2789-2937): lambda^e * key, negated when the
 // hit is the other point of the pair.  False when the hash is not a target (a bloom false positive).
+// kind KHB_ADDR_KIND_ETH (-c eth, keyhunt.cpp:2989-3002): the ETH address of key*G, the key returned unchanged.
 bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound* out);
 // lambda and lambda^2 mod n (keyhunt.cpp:582-583)
 const U256& endo_lambda(int e);

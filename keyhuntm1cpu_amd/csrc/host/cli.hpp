@@ -18,6 +18,7 @@ struct AddressCli {
   int search = 2;                     // -l (keyhunt.cpp:300: both)
   bool endomorphism = false;          // -e (keyhunt.cpp:579-585)
   bool crypto_set = false;            // -c given
+  bool eth = false;                   // -c eth: ETH addresses (-l is then not used for hashing)
   const char* stride = nullptr;       // -I
   bool random = false;                // -R
   bool quiet = false;                 // -q

@@ -1,5 +1,5 @@
 // keyhunt_amd -m address / -m rmd160: keyhunt.cpp main() (800-960 setup and prints, 2145-2252 stats)
-// and thread_process's output (writekey, keyhunt.cpp:5989-6030) over the libkhbsgs address scan.
+// and thread_process's output (writekey, keyhunt.cpp:5989-6030; writekeyeth, 6023-6051) over the libkhbsgs address scan.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,6 +9,7 @@
 #include <mutex>
 #include <thread>
 
+#include "../../../include/khbsgs.h"
 #include "address_host.hpp"
 #include "cli.hpp"
 
@@ -33,6 +34,21 @@ void writekey(const AddrFound& f, std::mutex& mu) {
   }
   printf("\nHit! Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", hexkey.c_str(), pubhex.c_str(), addr.c_str(),
          rmdhex);
+  fflush(stdout);
+}
+
+// writekeyeth (keyhunt.cpp:6023-6051)
+void writekeyeth(const AddrFound& f, std::mutex& mu) {
+  const std::string hexkey = f.key.hex();
+  char address[43] = "0x";
+  for (int i = 0; i < 20; ++i) snprintf(address + 2 + 2 * i, 3, "%02x", f.rmd[i]);
+  std::lock_guard<std::mutex> lk(mu);
+  FILE* keys = fopen("KEYFOUNDKEYFOUND.txt", "a+");
+  if (keys) {
+    fprintf(keys, "Private Key: %s\naddress: %s\n", hexkey.c_str(), address);
+    fclose(keys);
+  }
+  printf("\n Hit!!!! Private Key: %s\naddress: %s\n", hexkey.c_str(), address);
   fflush(stdout);
 }
 
@@ -81,7 +97,7 @@ int run_address_mode(const AddressCli& o) {
   // targets (keyhunt.cpp:6300-6358, 6559-6576)
   AddrTargets T;
   std::string err;
-  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err)) {
+  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err, o.eth)) {
     fprintf(stderr, "[E] %s\n[E] Unenexpected error\n", err.c_str());
     return EXIT_FAILURE;
   }
@@ -97,7 +113,7 @@ int run_address_mode(const AddressCli& o) {
   const uint32_t gpl = 16;
   G.build(stride, (uint32_t)(n_seq / 1024), gpl, o.threads > 0 ? o.threads : 1);
   AddrConfig cfg;
-  cfg.search = o.search;
+  cfg.search = o.eth ? KHB_SEARCH_ETH : o.search;   // -c eth: one hash per point whatever -l says
   cfg.endomorphism = o.endomorphism;
   cfg.start = start;
   cfg.end = end;
@@ -112,7 +128,7 @@ int run_address_mode(const AddressCli& o) {
   AddrStats stats;
   std::atomic<uint64_t> keys_done{0};
   AddrCallbacks cb;
-  cb.on_found = [&](const AddrFound& f) { writekey(f, out_mu); };
+  cb.on_found = [&](const AddrFound& f) { o.eth ? writekeyeth(f, out_mu) : writekey(f, out_mu); };
   cb.on_warning = [&](const std::string& m) {
     std::lock_guard<std::mutex> lk(out_mu);
     fprintf(stderr, "%s\n", m.c_str());
@@ -137,7 +153,7 @@ int run_address_mode(const AddressCli& o) {
       if (o.out_seconds && s % o.out_seconds == 0) {
         U256 total(keys_done.load());
         if (o.endomorphism) total = total * 6u;
-        else if (o.search == 1) total = total * 2u;
+        else if (o.search == 1) total = total * 2u;   // also with -c eth, as the reference (keyhunt.cpp:2183-2186)
         std::lock_guard<std::mutex> lk(out_mu);
         printf("\r%s\r", speed_line(total, s).c_str());
         fflush(stdout);

@@ -40,6 +40,7 @@ void menu() {
   printf("-h          show this help\n");
   printf("-B Mode     BSGS now have some modes <sequential, backward, both, random, dance>\n");
   printf("-b bits     For some puzzles you only need some numbers of bits in the test keys.\n");
+  printf("-c crypto   Search for specific crypto. <btc, eth> valid only w/ -m address\n");
   printf("-f file     Specify file name with public keys (02/03 compressed or 04 uncompressed hex)\n");
   printf("-k value    Use this only with bsgs mode, k value is factor for M, more speed but more RAM use wisely\n");
   printf("-m mode     mode of search for cryptos. (bsgs) default: bsgs\n");
@@ -296,10 +297,19 @@ int main(int argc, char** argv) {
     exit(EXIT_FAILURE);
   }
   if (mode == 1 || mode == 3) {
-    if (eth) {
-      fprintf(stderr, "[E] keyhunt_amd searches BTC P2PKH addresses only (-c eth is not available)\n");
+    if (eth && mode == 3) {           // -c is "valid only w/ -m address"
+      fprintf(stderr, "[E] -c eth is valid only with -m address (-m rmd160 searches BTC hash160 values)\n");
       exit(EXIT_FAILURE);
     }
+    if (eth && endomorphism) {
+      // keyhunt.cpp:2772 hashes beta*x a second time where beta^2*x was meant and recovers that slot with
+      // lambda^2, so the reference's -c eth -e can print a key that does not own the address
+      fprintf(stderr, "[E] -c eth does not work with -e: the reference's ETH endomorphism path hashes beta*x twice "
+                      "(beta^2*x is never hashed) and can report a key that does not own the address; it is not "
+                      "reproduced\n");
+      exit(EXIT_FAILURE);
+    }
+    ao.eth = eth;                     // keyhunt.cpp:2776-2780, 2989-3002
     ao.endomorphism = endomorphism;   // keyhunt.cpp:2646-2937 (BTC)
     ao.mode = mode;
     ao.random = bsgs_mode == 3;

@@ -392,15 +392,16 @@ int khh_parse_pubkey(const char* hex, uint8_t out_xy[64], int* compressed) {
   return 0;
 }
 
-khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
-                       uint32_t gpl, int threads, char* err, size_t errlen) {
+static khh_addr* addr_new(bool eth, const char* text, int bloom_multiplier, const uint8_t stride_be[32],
+                          uint64_t n_seq, uint32_t gpl, int threads, char* err, size_t errlen) {
   if (!text || n_seq < 1024 || n_seq % 1024) {
     set_err(err, errlen, "n must be a positive multiple of 1024");
     return nullptr;
   }
   khh_addr* a = new khh_addr();
   std::string e;
-  if (!AddrTargets::load_text(text, bloom_multiplier, a->T, &e)) {
+  if (!(eth ? AddrTargets::load_text_eth(text, bloom_multiplier, a->T, &e)
+            : AddrTargets::load_text(text, bloom_multiplier, a->T, &e))) {
     set_err(err, errlen, e);
     delete a;
     return nullptr;
@@ -417,7 +418,19 @@ khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t str
   return a;
 }
 
+khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
+                       uint32_t gpl, int threads, char* err, size_t errlen) {
+  return addr_new(false, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+}
+
+khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
+                           uint32_t gpl, int threads, char* err, size_t errlen) {
+  return addr_new(true, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+}
+
 void khh_addr_free(khh_addr* a) { delete a; }
+
+uint64_t khh_addr_skipped(const khh_addr* a) { return a ? a->T.skipped.size() : 0; }
 
 const uint8_t* khh_addr_table(const khh_addr* a, uint64_t* n) {
   if (n) *n = a->T.table.size();
@@ -459,7 +472,11 @@ int khh_addr_search_ex(const khh_addr* a, const uint8_t start_be[32], const uint
                        uint64_t* stats_out, uint32_t stats_len, char* err, size_t errlen) {
   const bool endo = search >= 0 && (search & KHB_SEARCH_ENDOMORPHISM);
   if (endo) search &= ~KHB_SEARCH_ENDOMORPHISM;
-  if (!a || !start_be || !end_be || search < 0 || search > 2) return KHB_EINVAL;
+  if (!a || !start_be || !end_be) return KHB_EINVAL;
+  if (search != KHB_SEARCH_ETH && (search < 0 || search > 2)) {
+    set_err(err, errlen, "search must be 0, 1 or 2 (-l), optionally with KHB_SEARCH_ENDOMORPHISM, or KHB_SEARCH_ETH alone");
+    return KHB_EINVAL;
+  }
   AddrConfig cfg;
   cfg.search = search;
   cfg.endomorphism = endo;
@@ -513,6 +530,8 @@ int khh_addr_confirm(const khh_addr* a, const uint8_t key_be[32], uint32_t kind,
   if (compressed) *compressed = f.compressed ? 1 : 0;
   return 1;
 }
+
+void khh_eth_address(const uint8_t xy[64], uint8_t out[20]) { eth_address_xy(xy, out); }
 
 void khh_hash160(const uint8_t xy[64], int compressed, uint8_t out[20]) {
   hash160_pub(pt_from_be(xy), compressed != 0, out);

@@ -1,4 +1,4 @@
-// libkhbsgs.so: the self-test entry points of include/khbsgs.h (field operations, bloom probe, hash160) with their
+// libkhbsgs.so: the self-test entry points of include/khbsgs.h (field operations, bloom probe, hash160 / ETH address) with their
 // kernels, and the point dumps of the two walks (khb_dump_x, khb_addr_dump).  Synchronous, on slot 0.
 #include "abi.hpp"
 
@@ -47,6 +47,20 @@ __global__ void k_probe(const uint8_t* __restrict__ bloom, BloomGeom g, const Fe
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   hit[i] = bloom_probe_x(bloom, g, xs[i]) ? 1 : 0;
+}
+
+// khb_hash160 kind 3: the ETH address (device/keccak.hpp) of any 64 bytes x||y, same record as k_hash160.
+__global__ void k_eth_address(const Fe* __restrict__ xy, const uint8_t* __restrict__ bloom, BloomGeom g,
+                              uint8_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fe x = xy[2 * i], y = xy[2 * i + 1];
+  uint32_t h[5];
+  eth_address(h, x, y);
+  uint8_t* o = out + 21 * (size_t)i;
+  for (int k = 0; k < 5; ++k)
+    for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(h[k] >> (8 * b));
+  o[20] = bloom ? (bloom_check20(bloom, g, h) ? 1 : 0) : 0;
 }
 
 // khb_dump_x (kind 1: x of every point of the bsgs walk, 32 bytes each) and khb_addr_dump (kind 2: x||y of the
@@ -135,7 +149,7 @@ int khb_probe(khb_ctx* c, const uint8_t* xs, uint8_t* hit, uint32_t n) {
 }
 
 int khb_hash160(khb_ctx* c, int kind, const uint8_t* xy, uint8_t* out, uint32_t n) {
-  if (!c || !xy || !out || n == 0 || kind < 0 || kind > 2) return KHB_EINVAL;
+  if (!c || !xy || !out || n == 0 || kind < 0 || kind > 3) return KHB_EINVAL;
   KHB_TRY(c, hipSetDevice(c->device));
   Slot& S = c->slot[0];
   std::vector<AffPt> h;
@@ -146,8 +160,12 @@ int khb_hash160(khb_ctx* c, int kind, const uint8_t* xy, uint8_t* out, uint32_t 
   KHB_TRY(c, d.alloc(n));
   KHB_TRY(c, dout.alloc(21 * (size_t)n));
   KHB_TRY(c, hipMemcpy(d, h.data(), sizeof(AffPt) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_hash160, dim3((n + 255) / 256), dim3(256), 0, S.stream, (const Fe*)d.p, kind, c->d_abloom,
-                     c->ageom, dout, n);
+  if (kind == 3)
+    hipLaunchKernelGGL(k_eth_address, dim3((n + 255) / 256), dim3(256), 0, S.stream, (const Fe*)d.p, c->d_abloom,
+                       c->ageom, dout, n);
+  else
+    hipLaunchKernelGGL(k_hash160, dim3((n + 255) / 256), dim3(256), 0, S.stream, (const Fe*)d.p, kind, c->d_abloom,
+                       c->ageom, dout, n);
   if (const int rc = sync_launch(c, S.stream)) return rc;
   KHB_TRY(c, hipMemcpy(out, dout, 21 * (size_t)n, hipMemcpyDeviceToHost));
   return KHB_OK;

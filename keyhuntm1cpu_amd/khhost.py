@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 7                 # include/khhost.h
+KHH_ABI_VERSION = 8                 # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
 KHH_RESIDENT_INFO = 8
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
@@ -97,7 +97,12 @@ def lib() -> C.CDLL:
         L.khh_addr_new.restype = C.c_void_p
         L.khh_addr_new.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p,
                                    C.c_size_t]
+        L.khh_addr_new_eth.restype = C.c_void_p
+        L.khh_addr_new_eth.argtypes = L.khh_addr_new.argtypes
         L.khh_addr_free.argtypes = [C.c_void_p]
+        L.khh_addr_skipped.restype = C.c_uint64
+        L.khh_addr_skipped.argtypes = [C.c_void_p]
+        L.khh_eth_address.argtypes = [C.c_char_p, C.c_char_p]
         L.khh_addr_table.restype = P(C.c_uint8)
         L.khh_addr_table.argtypes = [C.c_void_p, P(C.c_uint64)]
         L.khh_addr_bloom.restype = P(C.c_uint8)
@@ -451,16 +456,33 @@ def rmd_to_address(rmd: bytes) -> str:
     return out.value.decode()
 
 
+def eth_address(xy: bytes) -> bytes:
+    """ETH address of a public key x||y (64 bytes BE): bytes 12..31 of Keccak-256(x||y)."""
+    if len(xy) != 64:
+        raise ValueError("eth_address: 64 bytes x||y")
+    out = C.create_string_buffer(20)
+    lib().khh_eth_address(bytes(xy), out)
+    return out.raw
+
+
 class Addr:
-    """-m address targets (a target file's text) + generator for chunks of n_seq keys."""
+    """-m address targets (a target file's text) + generator for chunks of n_seq keys.  crypto="eth": the text is
+    read as -c eth reads it (ETH addresses) and the handle is searched with KHB_SEARCH_ETH."""
 
     def __init__(self, text: str, n_seq: int = 1 << 32, stride: int = 1, gpl: int = 16, bloom_multiplier: int = 1,
-                 threads: int = 0):
+                 threads: int = 0, crypto: str = "btc"):
+        if crypto not in ("btc", "eth"):
+            raise ValueError("crypto: btc or eth")
         err = C.create_string_buffer(256)
-        self.h = lib().khh_addr_new(text.encode(), bloom_multiplier, _b32(stride), n_seq, gpl, threads, err, 256)
+        new = lib().khh_addr_new_eth if crypto == "eth" else lib().khh_addr_new
+        self.h = new(text.encode(), bloom_multiplier, _b32(stride), n_seq, gpl, threads, err, 256)
         if not self.h:
             raise KhhError(err.value.decode())
-        self.n_seq, self.stride = n_seq, stride
+        self.n_seq, self.stride, self.crypto = n_seq, stride, crypto
+
+    def skipped(self) -> int:
+        """Lines the loader omitted as invalid."""
+        return int(lib().khh_addr_skipped(self.h))
 
     def close(self) -> None:
         if self.h:
@@ -520,7 +542,7 @@ class Addr:
     def search(self, start: int, end: int, search: int = 2, devices=(0,), lanes: int = 0, max_chunks: int = 0,
                random_chunks: bool = False, cap: int = 4096):
         """Found [(key, compressed, rmd160)] in discovery order, plus stats.  search | 4 (KHB_SEARCH_ENDOMORPHISM)
-        is -e."""
+        is -e; search = 8 (KHB_SEARCH_ETH) on a crypto="eth" handle gives (key, False, address)."""
         keys = C.create_string_buffer(32 * cap)
         comp = C.create_string_buffer(cap)
         rmd = C.create_string_buffer(20 * cap)

@@ -2,8 +2,10 @@
 MI355X, sequential chunks of -n keys from 2^70 (puzzle #71's range), reported as Mkeys/s with the
 VALU roofline of the hash path.  Prints one JSON line.
 
-Usage: python tools/bench_address.py [--search 2] [--chunks 24] [--n 0x100000000]
+Usage: python tools/bench_address.py [--search 2] [--chunks 24] [--n 0x100000000] [--crypto btc|eth]
 (24 chunks of 2^32 keys = three launches of eight work items per lane, two queued at a time.)
+--crypto eth: keyhunt -m address -c eth -f tests/1to32.eth over the same range and chunking (--search is not read:
+one Keccak-256 per key).
 """
 from __future__ import annotations
 
@@ -24,6 +26,11 @@ SHA_BLOCK, RMD_BLOCK, EC_PER_KEY = 2032, 1440, 680
 OPS = {0: 2 * SHA_BLOCK + RMD_BLOCK + EC_PER_KEY,            # uncompressed: 65-byte message, 2 blocks
        1: 2 * (SHA_BLOCK + RMD_BLOCK) + EC_PER_KEY - 150,    # compressed 02 + 03 from x (no y)
        2: 4 * SHA_BLOCK + 3 * RMD_BLOCK + EC_PER_KEY}
+# -c eth: one Keccak-f[1600] per key (device/keccak.hpp).  A round in 64-bit operations: theta 20 xor (column
+# parities) + 5 rotate + 5 xor (D) + 25 xor (A ^ D), rho 24 rotate, chi 25 x (not, and, xor), iota 1 xor = 155, each
+# two 32-bit operations (a rotation is one funnel shift per half): 310 x 24 rounds, + 16 byte swaps of x || y.
+KECCAK_F = 24 * 310
+OPS_ETH = KECCAK_F + 16 + EC_PER_KEY
 # Executed VALU lane-instructions per key, -l both (rocprofv3 --pmc SQ_INSTS_VALU x 64 / keys of one
 # 8-chunk launch, profiles/r02w/addr_valu_counter_collection.csv: 4.968e12 wave-instr x 64 / 2^35 keys;
 # VALUBusy 101.5 %: the kernel is at the VALU issue ceiling).
@@ -37,25 +44,32 @@ def main() -> None:
     ap.add_argument("--chunks", type=int, default=24)
     ap.add_argument("--n", type=lambda s: int(s, 0), default=1 << 32)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--crypto", choices=["btc", "eth"], default="btc", help="eth: -c eth over tests/1to32.eth")
     args = ap.parse_args()
+    eth = args.crypto == "eth"
+    search = 8 if eth else args.search           # KHB_SEARCH_ETH
+    ops = OPS_ETH if eth else OPS[args.search]
+    targets = "1to32.eth" if eth else "unsolvedpuzzles.rmd"
     import torch  # noqa: F401  (share torch's HIP runtime, as bench.py)
-    from keyhuntm1cpu_amd import khhost
-    with open(os.path.join(REPO, "tests", "golden", "address", "unsolvedpuzzles.rmd")) as f:
+    from keyhuntm1cpu_amd import khbsgs, khhost
+    with open(os.path.join(REPO, "tests", "golden", "address", targets)) as f:
         text = f.read()
+    build = khbsgs.build_info()                  # the line names the kernel build it measured, as bench.py's does
+    build["path"] = os.path.relpath(build["path"], REPO)
     t0 = time.time()
-    A = khhost.Addr(text, n_seq=args.n, threads=16)
+    A = khhost.Addr(text, n_seq=args.n, threads=16, crypto=args.crypto)
     t_build = time.time() - t0
     start = 1 << 70
     if args.warmup:
-        A.search(start, start + args.warmup * args.n, search=args.search)
+        A.search(start, start + args.warmup * args.n, search=search)
     t0 = time.time()
     found, st = A.search(start + args.warmup * args.n, start + (args.warmup + args.chunks) * args.n,
-                         search=args.search)
+                         search=search)
     dt = time.time() - t0
     keys = st["keys"]
     rate = keys / dt
     kern = st["kernel_s"] / max(1, st["launches"])
-    achieved = OPS[args.search] * keys / st["kernel_s"] / 1e12
+    achieved = ops * keys / st["kernel_s"] / 1e12
     out = {
         "metric": "Mkeys/s (-m address, keys hashed and probed per second)",
         "value": round(rate / 1e6, 2),
@@ -63,19 +77,22 @@ def main() -> None:
         "n_gpus": 1,
         "keys": keys,
         "seconds": round(dt, 3),
-        "search": ["uncompress", "compress", "both"][args.search],
-        "reference_keys_per_s": round(rate * (2 if args.search == 1 else 1) / 1e6, 2),
-        "config": {"workload": "-m address -f tests/unsolvedpuzzles.rmd -b 71 (BASELINE configs[4])",
+        "search": "eth" if eth else ["uncompress", "compress", "both"][args.search],
+        "reference_keys_per_s": round(rate * (2 if args.search == 1 and not eth else 1) / 1e6, 2),
+        "config": {"workload": "-m address -c eth -f tests/1to32.eth -b 71" if eth else
+                               "-m address -f tests/unsolvedpuzzles.rmd -b 71 (BASELINE configs[4])",
+                   "build": build,
                    "targets": len(A.table()), "n_seq": hex(args.n), "chunks": st["chunks"],
                    "launches": st["launches"], "bloom_hits": st["hits"], "found": len(found),
                    "table_build_s": round(t_build, 2)},
         "roofline": {"bound": "valu", "unit": "Tops/s", "achieved": round(achieved, 3), "peak": PEAK_T,
-                     "frac": round(achieved / PEAK_T, 4), "ops_per_key": OPS[args.search],
-                     "achieved_wall": round(OPS[args.search] * rate / 1e12, 3),
-                     "frac_wall": round(OPS[args.search] * rate / 1e12 / PEAK_T, 4),
-                     "kernel": "k_giant_scan<address>", "kernel_ms_avg": round(kern * 1e3, 3)},
+                     "frac": round(achieved / PEAK_T, 4), "ops_per_key": ops,
+                     "achieved_wall": round(ops * rate / 1e12, 3),
+                     "frac_wall": round(ops * rate / 1e12 / PEAK_T, 4),
+                     "kernel": "k_giant_scan<address>", "kernel_ms_avg": round(kern * 1e3, 3),
+                     "shader_mhz": round(st["shader_mhz"], 1)},
     }
-    if args.search in EXEC_PER_KEY:
+    if not eth and args.search in EXEC_PER_KEY:
         e = EXEC_PER_KEY[args.search]
         out["roofline"]["executed"] = {
             "valu_lane_instr_per_key": e, "valu_busy_pct": 101.5,

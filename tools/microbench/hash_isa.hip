@@ -5,6 +5,7 @@
 // per thread, loads/stores of the operands included (≈ 25 instructions).
 #include <hip/hip_runtime.h>
 #include "device/hash160.hpp"
+#include "device/keccak.hpp"
 using namespace khb;
 
 // hash160 of both compressed keys 02 || x and 03 || x in one scope: the two messages differ only in
@@ -63,4 +64,15 @@ __global__ void k_xxh64_pair(const uint32_t* in, uint64_t* out) {       // the b
   for (int k = 0; k < 5; ++k) h[k] = in[i * 5 + k];
   const uint64_t a = xxh64_20(h, KHB_BLOOM_SEED);
   out[i] = a ^ xxh64_20(h, a);
+}
+__global__ void k_eth_address(const uint32_t* in, uint32_t* out) {          // -c eth: one Keccak-f[1600] of x || y
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  Fe x, y;
+  for (int k = 0; k < 8; ++k) {
+    x.v[k] = in[i * 16 + k];
+    y.v[k] = in[i * 16 + 8 + k];
+  }
+  uint32_t o[5];
+  eth_address(o, x, y);
+  for (int k = 0; k < 5; ++k) out[i * 5 + k] = o[k];
 }
