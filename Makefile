@@ -1,7 +1,7 @@
 # Build everything in-tree (the .so / binaries travel to the GPU box with the repo snapshot).
 #   keyhuntm1cpu_amd/lib/libkhbsgs.so   HIP giant-step library (gfx950), include/khbsgs.h
 #   keyhuntm1cpu_amd/lib/libkhhost.so   C++ host engine, include/khhost.h
-#   keyhuntm1cpu_amd/bin/keyhunt_amd    keyhunt-compatible CLI (-m bsgs, -m address, -m rmd160)
+#   keyhuntm1cpu_amd/bin/keyhunt_amd    keyhunt-compatible CLI (-m bsgs, -m address, -m rmd160, -m xpoint)
 #   keyhuntm1cpu_amd/bin/bsgsd_amd      bsgsd-compatible TCP daemon
 #   oracle/build/liboracle.so           test-only checker (oracle/Makefile)
 HIPCC    ?= /opt/rocm/bin/hipcc
@@ -17,7 +17,7 @@ CXXFLAGS ?= -O3 -std=c++17 -fPIC -march=x86-64-v3 -Wall -Wextra -Wno-unused-func
 DEV_HDRS  := $(wildcard $(CSRC)/device/*.hpp) $(CSRC)/scan_kernels.hpp $(CSRC)/abi.hpp include/khbsgs.h
 # libkhbsgs: the C ABI by concern (khbsgs, khb_tables, khb_selftest, k_check; abi.hpp) + one translation unit per
 # group of k_giant_scan instances, so `make -j` compiles the heavy kernels in parallel
-HIP_SRCS  := $(CSRC)/khbsgs.hip $(CSRC)/khb_tables.hip $(CSRC)/khb_selftest.hip $(CSRC)/k_bsgs.hip $(CSRC)/k_addr.hip $(CSRC)/k_addr_e.hip $(CSRC)/k_addr_eth.hip $(CSRC)/k_baby.hip \
+HIP_SRCS  := $(CSRC)/khbsgs.hip $(CSRC)/khb_tables.hip $(CSRC)/khb_selftest.hip $(CSRC)/k_bsgs.hip $(CSRC)/k_addr.hip $(CSRC)/k_addr_e.hip $(CSRC)/k_addr_eth.hip $(CSRC)/k_addr_x.hip $(CSRC)/k_baby.hip \
              $(CSRC)/k_check.hip
 HIP_OBJS  := $(patsubst $(CSRC)/%.hip,build/hip/%.o,$(HIP_SRCS))
 HOST_SRCS := $(CSRC)/host/u256.cpp $(CSRC)/host/secp_host.cpp $(CSRC)/host/bloom_host.cpp \

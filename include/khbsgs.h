@@ -54,7 +54,9 @@ extern "C" {
  * line's build record, which tests/test_launch.py pins to "7", keeps naming the same scan ABI); a caller that needs
  * them checks for the khb_build_l1_resident symbol.  -m address -c eth (KHB_SEARCH_ETH, KHB_ADDR_KIND_ETH and
  * khb_hash160 kind 3) is an addition of the same sort: new values of existing arguments, version 7; a caller that
- * needs it checks for KHB_SEARCH_ETH in this header, and a library without it answers KHB_EINVAL. */
+ * needs it checks for KHB_SEARCH_ETH in this header, and a library without it answers KHB_EINVAL.  -m xpoint
+ * (KHB_SEARCH_XPOINT, KHB_ADDR_KIND_X and khb_hash160 kind 4) likewise: new values of existing arguments, version 7;
+ * a caller checks for KHB_SEARCH_XPOINT here, and a library without it answers KHB_EINVAL. */
 #define KHB_ABI_VERSION 7
 int khb_abi_version(void);
 /* What this library was built as, one line of `key=value` words: abi, arch, variant ("product" for the in-tree
@@ -275,9 +277,11 @@ typedef struct {
                         (x, y), 3 = uncompressed (x, p - y), the negated point (-e only).  e: the point itself (0),
                         or with -e (beta*x, y) = lambda*P (1) and (beta^2*x, y) = lambda^2*P (2), keyhunt.cpp:2646-2763.
                         Without -e kind is 0, 1 or 2 as before.  KHB_ADDR_KIND_ETH: the ETH address of the point
-                        (KHB_SEARCH_ETH). */
+                        (KHB_SEARCH_ETH).  KHB_ADDR_KIND_X | e << 2: the first 20 bytes of x (e = 0), beta*x (1) or
+                        beta^2*x (2) of the point (KHB_SEARCH_XPOINT; e != 0 only with -e). */
 } khb_addr_hit;
 #define KHB_ADDR_KIND_ETH 16   /* disjoint from form | e << 2 (at most 11) */
+#define KHB_ADDR_KIND_X 32     /* | e << 2 (32, 36, 40): disjoint from the BTC kinds and from KHB_ADDR_KIND_ETH */
 
 /* The single target bloom of -m address (bloom over 20-byte values, hash160s or with -c eth addresses,
  * initBloomFilter, keyhunt.cpp:6559-6576). */
@@ -293,9 +297,15 @@ int khb_load_addr_bloom(khb_ctx* ctx, const uint8_t* bf, uint64_t bytes, uint64_
  * 12..31 of the digest probed in the bloom; hits have kind KHB_ADDR_KIND_ETH and the host confirms them with the
  * point's own key.  Exactly that value: combined with KHB_SEARCH_ENDOMORPHISM or with -l bits it is KHB_EINVAL
  * (the reference's -c eth -e hashes beta*x twice where beta^2*x was meant, keyhunt.cpp:2772, and can report a
- * key that does not own the address; it is not reproduced). */
+ * key that does not own the address; it is not reproduced).
+ * search == KHB_SEARCH_XPOINT (-m xpoint, keyhunt.cpp:3005-3062), alone or OR'ed with KHB_SEARCH_ENDOMORPHISM: no hash,
+ * the first 20 bytes of each point's big-endian x are probed in the bloom (a bloom over such 20-byte values), with
+ * -e also those of beta*x and beta^2*x; y is never computed.  Hits have kind KHB_ADDR_KIND_X | e << 2 and the host
+ * confirms them with lambda^e * key, no sign fix-up.  With -l bits or KHB_SEARCH_ETH it is KHB_EINVAL and nothing is
+ * queued. */
 #define KHB_SEARCH_ENDOMORPHISM 4
 #define KHB_SEARCH_ETH 8
+#define KHB_SEARCH_XPOINT 16
 int khb_addr_submit(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, uint32_t group_begin,
                     uint32_t group_count, int search);
 /* stats->n_cand = number of bloom hits (may exceed cap); giant_steps = keys scanned. */
@@ -305,8 +315,9 @@ int khb_addr_scan(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, u
 /* parity: x||y (64 bytes BE per point, t = 0..1023 per group) of ONE job. */
 int khb_addr_dump(khb_ctx* ctx, const uint8_t* centre_xy_be, uint32_t group_begin, uint32_t group_count,
                   uint8_t* xy);
-/* self-test: out[21*i] = hash160 (20 bytes) of point i (x||y BE) for kind 0/1/2, or its ETH address for kind 3
- * (any 64 bytes: the hash does not need a point of the curve), then one byte = bloom_check20 result against the
+/* self-test: out[21*i] = hash160 (20 bytes) of point i (x||y BE) for kind 0/1/2, its ETH address for kind 3
+ * (any 64 bytes: the hash does not need a point of the curve), or for kind 4 the first 20 bytes of x as -m xpoint
+ * probes them (x < p; y is not read), then one byte = bloom_check20 result against the
  * loaded address bloom (0 when none is loaded). */
 int khb_hash160(khb_ctx* ctx, int kind, const uint8_t* xy_be, uint8_t* out, uint32_t n);
 

@@ -21,8 +21,10 @@ extern "C" {
  * A binding checks khh_abi_version() == the KHH_ABI_VERSION it was written for before any other call.
  * ABI 7 added resident tables (large -k): khh_tables_new_resident and the khh_session_resident_* calls.
  * ABI 8 added -m address -c eth: khh_addr_new_eth, khh_addr_skipped, khh_eth_address, search = KHB_SEARCH_ETH and
- * khh_addr_confirm's kind KHB_ADDR_KIND_ETH. */
-#define KHH_ABI_VERSION 8
+ * khh_addr_confirm's kind KHB_ADDR_KIND_ETH.
+ * ABI 9 added -m xpoint: khh_addr_new_xpoint, khh_addr_counted, search = KHB_SEARCH_XPOINT (optionally with
+ * KHB_SEARCH_ENDOMORPHISM) and khh_addr_confirm's kinds KHB_ADDR_KIND_X | e << 2. */
+#define KHH_ABI_VERSION 9
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -158,7 +160,7 @@ uint64_t khh_session_recorded(const khh_session* s, uint8_t* bases_be, uint32_t*
 int khh_pubkey(const uint8_t key_be[32], uint8_t out_xy[64]);
 int khh_parse_pubkey(const char* hex, uint8_t out_xy[64], int* compressed);
 
-/* ---- -m address / -m rmd160 (BTC P2PKH, and ETH addresses with -c eth) ----
+/* ---- -m address / -m rmd160 (BTC P2PKH, and ETH addresses with -c eth) and -m xpoint ----
  * Targets from a target file's text (base58 addresses or 40-hex rmd160 lines, keyhunt.cpp:6300-6358).
  * The generator (Gn table + lane offsets for chunks of n_seq keys) is built for stride and gpl. */
 typedef struct khh_addr khh_addr;
@@ -171,9 +173,25 @@ khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t str
  * the mismatch is an error return with a message, not an empty search. */
 khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                            uint32_t gpl, int threads, char* err, size_t errlen);
+/* -m xpoint: targets as forceReadFileXPoint reads them (keyhunt.cpp:6454-6552).  Lines are trimmed of " \t\n\r";
+ * lines of 40 or more characters are counted, the count sizes the bloom (initBloomFilter and the multiplier) and is
+ * also the number of lines read from the top of the text, as in the reference.  The first token of a line
+ * (separators: space, tab, ':') decides: 64 hex characters are x; 66 are a compressed key whose two prefix
+ * characters are dropped without being checked; 130 are an uncompressed key.  A token of any other length or with a
+ * non-hex character is skipped (khh_addr_skipped) and not stored in the table.  The table holds the first 20 bytes
+ * of x, sorted by memcmp, and the bloom the same 20 bytes.
+ * One deliberate deviation: for a 130-character line the reference adds 04 || x[0..18] to the bloom and stores
+ * x[1..20] in the table (keyhunt.cpp:6524-6528, offsets 0 and 2 where 1 was meant), so an uncompressed line can
+ * never be found there; here both take x[0..19].
+ * Such a handle is searched with KHB_SEARCH_XPOINT (16), alone or OR'ed with KHB_SEARCH_ENDOMORPHISM, only, and no
+ * other handle ever with it: the mismatch is an error return with a message, as for -c eth. */
+khh_addr* khh_addr_new_xpoint(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
+                              uint32_t gpl, int threads, char* err, size_t errlen);
 void khh_addr_free(khh_addr* a);
 /* lines the loader omitted ("[I] Ommiting invalid line") */
 uint64_t khh_addr_skipped(const khh_addr* a);
+/* lines the loader counted (they size the bloom) */
+uint64_t khh_addr_counted(const khh_addr* a);
 /* sorted 20-byte table (n entries) and the target bloom */
 const uint8_t* khh_addr_table(const khh_addr* a, uint64_t* n);
 const uint8_t* khh_addr_bloom(const khh_addr* a, uint64_t* bytes, uint64_t* bits, uint32_t* hashes);
@@ -182,7 +200,8 @@ uint32_t khh_addr_lane_offsets(const khh_addr* a, uint8_t* out /* n*64, may be N
 /* Sequential (random_chunks = 0) or -R search of [start, end) with search 0/1/2 (-l), OR'ed with
  * KHB_SEARCH_ENDOMORPHISM (4, include/khbsgs.h) for -e: the found keys are then lambda^e multiples too; or with
  * search = KHB_SEARCH_ETH (8) alone on a khh_addr_new_eth handle: found keys come back with compressed = 0 and the
- * 20 address bytes in rmd.  Found keys
+ * 20 address bytes in rmd; or with search = KHB_SEARCH_XPOINT (16), alone or with KHB_SEARCH_ENDOMORPHISM, on a
+ * khh_addr_new_xpoint handle: compressed = 0 and the matched first 20 bytes of x in rmd.  Found keys
  * (32 B BE each) with compressed flags and rmd160s, in discovery order; *n_found may exceed cap.
  * Discovery order is batch order, and (chunk, key) order inside a batch, except after an overflow: a batch
  * whose bloom hits overflowed khb_addr_hit_capacity is rescanned in parts queued behind the batch already
@@ -207,7 +226,9 @@ int khh_addr_set_hit_capacity(khh_addr* a, uint32_t cap);
  * searchbinary of the hash the kind names, then the reference's key recovery (keyhunt.cpp:2789-2937; lambda^e * key,
  * negated for the other point of a compressed x or for form 3).  Returns 1 and the key / compressed flag when the
  * hash is a target, 0 when it is not.  kind KHB_ADDR_KIND_ETH (keyhunt.cpp:2989-3002): the ETH address of key*G
- * is looked up and the key returned unchanged. */
+ * is looked up and the key returned unchanged.  kind KHB_ADDR_KIND_X | e << 2 (keyhunt.cpp:3005-3062): the first 20
+ * bytes of beta^e * x(key*G) are looked up and lambda^e * key mod n returned (the key itself for e = 0), never
+ * negated, compressed = 0. */
 int khh_addr_confirm(const khh_addr* a, const uint8_t key_be[32], uint32_t kind, uint8_t out_key_be[32],
                      int* compressed);
 /* hash160 of a public key (x||y BE) and its P2PKH address (out_addr >= 36 bytes) */

@@ -1,11 +1,57 @@
-// -m address / -m rmd160: what the x,y walk does with each point (hash160 or, with -c eth, the ETH address + the
-// target bloom, or the x||y dump).
+// -m address / -m rmd160 / -m xpoint: what the walk does with each point (hash160, with -c eth the ETH address, or
+// for -m xpoint the first 20 bytes of x, + the target bloom; or the x||y dump).
 #pragma once
 #include "scan_args.hpp"
 #include "hash160.hpp"
 #include "keccak.hpp"
+#include "xpoint.hpp"
 
 namespace khbk {
+
+// beta (keyhunt.cpp:584): lambda*P = (beta*x, y).  beta^2*x is computed as beta*(beta*x), the same canonical value as
+// the reference's ModMulK1(x, beta2) (beta2 = beta^2 mod p, keyhunt.cpp:585), with one constant and no indexed table.
+__device__ __forceinline__ Fe fe_beta() {
+  return Fe{{0x719501eeu, 0xc1396c28u, 0x12f58995u, 0x9cf04975u, 0xac3434e9u, 0x6e64479eu, 0x657c0710u, 0x7ae96a2bu}};
+}
+
+// x, beta*x and beta^2*x of one point (-m xpoint -e).
+__device__ __forceinline__ void xpoint_endo(const ScanArgs& A, const Fe& x, uint32_t t, uint32_t job, uint32_t j) {
+  const Fe kBeta = fe_beta();
+  Fe xe = x;
+#pragma unroll 1
+  for (uint32_t e = 0; e < 3; ++e) {
+    if (e) {
+      fm_mul(xe, xe, kBeta);
+      fm_canon(xe, xe);
+    }
+    uint32_t h[5];
+    x_be20(h, xe);
+    if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, KHB_ADDR_KIND_X | (e << 2));
+  }
+}
+
+// -m xpoint handling of a walk step's two points (keyhunt.cpp:3005-3062): the first 20 bytes of each canonical x
+// probed in the target bloom (kind KHB_ADDR_KIND_X), with -e also those of beta*x and beta^2*x, each canonical before
+// it is serialised (kind KHB_ADDR_KIND_X | e << 2; keyhunt.cpp:3013-3043).  Without -e both serialisations stand
+// before either bloom load is issued.  TWO = false: x1 alone.
+template <int MODE, bool TWO>
+__device__ __forceinline__ void xpoint_probe(const ScanArgs& A, const Fe& x1, uint32_t t1, const Fe& x2, uint32_t t2,
+                                             uint32_t job, uint32_t j) {
+  static_assert(is_xpoint(MODE), "xpoint_probe: kAddrX or kAddrXE");
+  uint32_t h1[5], h2[5];
+  if constexpr (MODE == kAddrX) {
+    x_be20(h1, x1);
+    if constexpr (TWO) x_be20(h2, x2);
+    const bool b1 = bloom_check20(A.bloom, A.geom, h1);
+    const bool b2 = TWO && bloom_check20(A.bloom, A.geom, h2);
+    if (b1) emit_ahit(A, job, j, t1, KHB_ADDR_KIND_X);
+    if (b2) emit_ahit(A, job, j, t2, KHB_ADDR_KIND_X);
+  } else {
+    // one point after the other
+    xpoint_endo(A, x1, t1, job, j);
+    if constexpr (TWO) xpoint_endo(A, x2, t2, job, j);
+  }
+}
 
 // -m address handling of one point (keyhunt.cpp:2716-2937, BTC, no endomorphism): hash160 of
 // the compressed key for both prefixes from x alone (covers +k and -k, keyhunt.cpp:2719-2733) and/or
@@ -19,6 +65,8 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
     uint8_t* o = A.xdump + ((uint64_t)(j - A.group_begin) * KHB_GROUP + t) * 64;
     fe_to_be(o, x);
     fe_to_be(o + 32, y);
+  } else if constexpr (is_xpoint(MODE)) {
+    xpoint_probe<MODE, false>(A, x, t, x, t, job, j);   // y is not read
   } else if constexpr (MODE == kAddrEth) {
     // -c eth (keyhunt.cpp:2776-2780, 2989-3002): one Keccak-f[1600] per point; the address words are already in
     // bloom_check20's byte order
@@ -31,10 +79,7 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
       // -e (keyhunt.cpp:2646-2763): lambda*P = (beta*x, y) and lambda^2*P = (beta^2*x, y) (keyhunt.cpp:582-585).
       // Compressed: the 02 and 03 hashes of x, beta*x, beta^2*x (kinds 0|e<<2, 1|e<<2); uncompressed: (x_e, y) and
       // (x_e, p - y), the negated point (kinds 2|e<<2, 3|e<<2).  Every x_e is canonical before it is hashed.
-      // beta (keyhunt.cpp:584); beta^2*x is computed as beta*(beta*x), the same canonical value as the reference's
-      // ModMulK1(x, beta2) (beta2 = beta^2 mod p, keyhunt.cpp:585), with one constant and no indexed table
-      const Fe kBeta = {{0x719501eeu, 0xc1396c28u, 0x12f58995u, 0x9cf04975u, 0xac3434e9u, 0x6e64479eu, 0x657c0710u,
-                         0x7ae96a2bu}};
+      const Fe kBeta = fe_beta();
       Fe ny;
       if constexpr (addr_uncompressed(MODE)) {
         fm_sub(ny, fe_p(), y);                     // y != 0 on the curve: p - y is canonical

@@ -65,13 +65,18 @@ enum : int {
   kAddrCE = 11,    //   keyhunt.cpp:2646-2763)
   kAddrBE = 12,
   kAddrEth = 13,   // -m address -c eth: Keccak-256 of x || y (keyhunt.cpp:2776-2780; device/keccak.hpp)
+  kAddrX = 14,     // -m xpoint: the first 20 bytes of x probed as they are (keyhunt.cpp:3005-3062; device/xpoint.hpp)
+  kAddrXE = 15,    // kAddrX with -e: x, beta*x and beta^2*x (keyhunt.cpp:3013-3043)
 };
 constexpr bool is_gated(int m) { return m == kScanG || m == kScanG1 || m == kScanG2; }
 // filter stages in front of the full gate: 0 (kScanG), 1 (the fold, kScanG1), 2 (filter + fold, kScanG2)
 constexpr int gate_stages(int m) { return m == kScanG2 ? 2 : m == kScanG1 ? 1 : 0; }
 constexpr bool is_scan(int m) { return m == kScan || is_gated(m); }
-constexpr bool is_endo(int m) { return m >= kAddrUE && m <= kAddrBE; }
-constexpr bool is_addr(int m) { return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth; }
+constexpr bool is_endo(int m) { return m >= kAddrUE && m <= kAddrBE; }       // BTC -e (kAddrXE is is_xpoint)
+constexpr bool is_xpoint(int m) { return m == kAddrX || m == kAddrXE; }
+constexpr bool is_addr(int m) {
+  return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth || is_xpoint(m);
+}
 constexpr bool needs_y(int m) {
   return m == kAddrU || m == kAddrB || m == kAddrDump || m == kAddrUE || m == kAddrBE || m == kAddrEth;
 }
@@ -91,8 +96,14 @@ constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and
 // kernel time than 4 (128 VGPRs, 208 B of scratch) and 27 % less than 2 (profiles/eth)
 #define KHB_ADDR_ETH_WAVES_PER_SIMD 3
 #endif
+#ifndef KHB_ADDR_X_WAVES_PER_SIMD
+// occupancy target of the -m xpoint kernels: 3 waves (164 and 163 VGPRs, no scratch); at 4 (128 VGPRs) both kernels
+// spill, 184 and 192 B of scratch per lane (profiles/xpoint)
+#define KHB_ADDR_X_WAVES_PER_SIMD 3
+#endif
 constexpr int waves_per_simd(int m) {
   return m == kAddrEth ? KHB_ADDR_ETH_WAVES_PER_SIMD
+         : is_xpoint(m) ? KHB_ADDR_X_WAVES_PER_SIMD
          : is_endo(m)  ? KHB_ADDR_E_WAVES_PER_SIMD
          : is_addr(m)  ? KHB_ADDR_WAVES_PER_SIMD
                        : KHB_WAVES_PER_SIMD;

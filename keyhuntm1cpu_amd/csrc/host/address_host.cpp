@@ -174,14 +174,14 @@ static bool all_hex(const char* s) {
 
 static int hexv(char c) { return c <= '9' ? c - '0' : (c | 32) - 'a' + 10; }
 
-// Split like fgets(aux, 100, f): a line longer than 99 characters continues in the next read.
-static std::vector<std::string> fgets_lines(const std::string& text) {
+// Split like fgets(aux, size, f): a line longer than size - 1 characters continues in the next read.
+static std::vector<std::string> fgets_lines(const std::string& text, size_t size = 100) {
   std::vector<std::string> out;
   size_t p = 0;
   while (p < text.size()) {
     size_t e = text.find('\n', p);
     size_t len = (e == std::string::npos ? text.size() : e + 1) - p;
-    if (len > 99) len = 99;
+    if (len > size - 1) len = size - 1;
     out.push_back(text.substr(p, len));
     p += len;
   }
@@ -282,7 +282,49 @@ bool AddrTargets::load_text_eth(const std::string& text, int bloom_multiplier, A
   return true;
 }
 
-bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err, bool eth) {
+// forceReadFileXPoint (keyhunt.cpp:6454-6552): fgets(aux, 1000); lines of 40 or more characters size the bloom and
+// give the number of lines read from the top of the file (the reference's i runs over lines, valid or not).
+bool AddrTargets::load_text_xpoint(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err) {
+  T = AddrTargets();
+  T.xpoint = true;
+  const std::vector<std::string> lines = fgets_lines(text, 1000);
+  for (const std::string& l : lines) {
+    std::string a = l;
+    a.resize(strlen(a.c_str()));
+    std::vector<char> aux(a.begin(), a.end());
+    aux.push_back(0);
+    trim(aux.data());
+    if (strlen(aux.data()) >= 40) ++T.counted;
+  }
+  const uint64_t entries = T.counted <= 10000 ? 10000 : (uint64_t)(bloom_multiplier > 0 ? bloom_multiplier : 1) * T.counted;
+  if (T.bloom.init2(entries, 0.000001L) != 0) {
+    if (err) *err = "bloom_init failed";
+    return false;
+  }
+  for (size_t li = 0; li < T.counted && li < lines.size(); ++li) {
+    std::vector<char> aux(lines[li].c_str(), lines[li].c_str() + strlen(lines[li].c_str()) + 1);
+    trim(aux.data());
+    // stringtokenizer (util.c:67-84): trim "\t\n\r :", then the first strtok(" \t:") token
+    const char* tok = aux.data() + strspn(aux.data(), " \t:");
+    const size_t r = strcspn(tok, " \t:");
+    const std::string token(tok, r);
+    const char* hex = r == 64 || r == 130 ? token.c_str() : r == 66 ? token.c_str() + 2 : nullptr;
+    if (r == 130) hex += 2;          // 04 || x || y: x[0..19] for bloom and table (see address_host.hpp)
+    if (hex && all_hex(token.c_str())) {
+      H160 h;
+      for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(hex[2 * k]) * 16 + hexv(hex[2 * k + 1]));
+      T.bloom.add20(h.data());
+      T.table.push_back(h);
+    } else {
+      T.skipped.push_back(aux.data());
+    }
+  }
+  std::sort(T.table.begin(), T.table.end(),
+            [](const H160& a, const H160& b) { return memcmp(a.data(), b.data(), 20) < 0; });
+  return true;
+}
+
+bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err, int kind) {
   FILE* f = fopen(path, "r");
   if (!f) {
     if (err) *err = std::string("Error opening the file ") + path;
@@ -293,7 +335,9 @@ bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets&
   size_t n;
   while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
   fclose(f);
-  return eth ? load_text_eth(text, bloom_multiplier, T, err) : load_text(text, bloom_multiplier, T, err);
+  return kind == 2   ? load_text_xpoint(text, bloom_multiplier, T, err)
+         : kind == 1 ? load_text_eth(text, bloom_multiplier, T, err)
+                     : load_text(text, bloom_multiplier, T, err);
 }
 
 bool AddrTargets::searchbinary(const uint8_t data[20]) const {
@@ -379,7 +423,24 @@ bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound
     memcpy(out->rmd.data(), h, 20);
     return true;
   }
-  if (T.eth) return false;
+  if (kind & KHB_ADDR_KIND_X) {
+    // -m xpoint (keyhunt.cpp:3005-3062): searchbinary of the first 20 bytes of beta^e * x(key*G) = x(lambda^e*key*G);
+    // the reported key is lambda^e * key mod n, the walked key itself without -e, and never negated
+    const uint32_t e = (kind & ~(uint32_t)KHB_ADDR_KIND_X) >> 2;
+    if (!T.xpoint || (kind & 3u) || e > 2) return false;
+    U256 k;
+    U256::divmod(key, secp_order(), nullptr, &k);
+    if (e) k = mulmod(k, endo_lambda((int)e), secp_order());
+    if (k.is_zero()) return false;
+    uint8_t xy[64];
+    pt_to_be(xy, mul_g(k));
+    if (!T.searchbinary(xy)) return false;
+    out->key = e ? k : key;
+    out->compressed = false;
+    memcpy(out->rmd.data(), xy, 20);
+    return true;
+  }
+  if (T.eth || T.xpoint) return false;
   const uint32_t form = kind & 3u, e = kind >> 2;
   if (e > 2) return false;
   U256 k;
@@ -633,12 +694,15 @@ int addr_search(const AddrTargets& T, const AddrGen& G, const AddrConfig& cfg, c
     if (err) *err = "n must be a positive multiple of 1024";
     return -100;
   }
-  const bool eth = cfg.search == KHB_SEARCH_ETH;
-  if (eth != T.eth || (eth && cfg.endomorphism) || (!eth && (cfg.search < 0 || cfg.search > 2))) {
+  const bool eth = cfg.search == KHB_SEARCH_ETH, xpoint = cfg.search == KHB_SEARCH_XPOINT;
+  if (eth != T.eth || xpoint != T.xpoint || (eth && cfg.endomorphism) ||
+      (!eth && !xpoint && (cfg.search < 0 || cfg.search > 2))) {
     if (err)
-      *err = T.eth ? "targets loaded for -c eth are searched with KHB_SEARCH_ETH alone (no -l bits, no -e)"
-                   : eth ? "KHB_SEARCH_ETH needs targets loaded for -c eth (these are BTC hash160 targets)"
-                         : "search must be 0, 1 or 2 (-l), optionally with -e";
+      *err = T.eth      ? "targets loaded for -c eth are searched with KHB_SEARCH_ETH alone (no -l bits, no -e)"
+             : T.xpoint ? "targets loaded for -m xpoint are searched with KHB_SEARCH_XPOINT, optionally with -e (no -l bits)"
+             : eth      ? "KHB_SEARCH_ETH needs targets loaded for -c eth (these are BTC hash160 targets)"
+             : xpoint   ? "KHB_SEARCH_XPOINT needs targets loaded for -m xpoint (these are BTC hash160 targets)"
+                        : "search must be 0, 1 or 2 (-l), optionally with -e";
     return KHB_EINVAL;
   }
   if ((cfg.n_seq / 1024 + G.gpl - 1) / G.gpl > G.offs.size()) {

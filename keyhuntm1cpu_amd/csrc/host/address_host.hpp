@@ -1,5 +1,6 @@
-// Host side of keyhunt's -m address / -m rmd160 modes (BTC P2PKH, with or without -e; -c eth) on libkhbsgs:
-// target loading (forceReadFileAddress, keyhunt.cpp:6300-6358; forceReadFileAddressEth, 6374-6450), the generator table
+// Host side of keyhunt's -m address / -m rmd160 (BTC P2PKH, with or without -e; -c eth) and -m xpoint modes on
+// libkhbsgs: target loading (forceReadFileAddress, keyhunt.cpp:6300-6358; forceReadFileAddressEth, 6374-6450;
+// forceReadFileXPoint, 6454-6552), the generator table
 // (init_generator, keyhunt.cpp:4386-4399), chunk claiming (thread_process, keyhunt.cpp:2546-2567),
 // and the confirmation of GPU bloom hits (searchbinary + key recovery, keyhunt.cpp:2789-2937).
 #pragma once
@@ -36,13 +37,22 @@ struct AddrTargets {
   uint64_t counted = 0;                // lines longer than 20 characters (sizes the bloom)
   std::vector<std::string> skipped;    // "[I] Ommiting invalid line"
   bool eth = false;                    // -c eth: the table holds ETH addresses (load_text_eth)
+  bool xpoint = false;                 // -m xpoint: the table holds the first 20 bytes of x (load_text_xpoint)
 
   // text: the target file's contents.  Returns false with *err on an unusable bloom.
   static bool load_text(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
   // -c eth: 40-hex lines, with or without a two-character prefix (forceReadFileAddressEth); counted = lines of
   // 40 or more characters
   static bool load_text_eth(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
-  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err, bool eth = false);
+  // -m xpoint (forceReadFileXPoint, keyhunt.cpp:6454-6552): counted = lines of 40 or more characters, and that many
+  // lines are read from the top of the file.  The first token (separators: space, tab, ':') decides: 64 hex = x,
+  // 66 hex = a compressed key whose two prefix characters are dropped unchecked, 130 hex = an uncompressed key;
+  // anything else goes to `skipped` and not into the table (the reference keeps a zero entry for it).  Table and
+  // bloom hold the first 20 bytes of x.  Deviation: for a 130-hex line the reference adds 04 || x[0..18] to the bloom
+  // and stores x[1..20] in the table (6524-6528), so such a line can never be found there; here both take x[0..19].
+  static bool load_text_xpoint(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
+  // kind: 0 = load_text, 1 = load_text_eth, 2 = load_text_xpoint
+  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err, int kind = 0);
   bool searchbinary(const uint8_t h[20]) const;   // keyhunt.cpp:2311-2335, literal
 };
 
@@ -57,9 +67,10 @@ struct AddrGen {
 };
 
 struct AddrConfig {
-  int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300), or
-                                       // KHB_SEARCH_ETH (-c eth; the targets must be load_text_eth's)
-  bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and negated points
+  int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300),
+                                       // KHB_SEARCH_ETH (-c eth; the targets must be load_text_eth's) or
+                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be load_text_xpoint's)
+  bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and (BTC) negated points
   U256 start{1}, end{1};               // [start, end): n_range_start / n_range_end
   uint64_t n_seq = 1ull << 32;         // keys per claimed chunk (-n, N_SEQUENTIAL_MAX)
   bool random = false;                 // -R: each chunk starts at a random key in [start, end)
@@ -73,7 +84,7 @@ struct AddrConfig {
 struct AddrFound {
   U256 key;
   bool compressed;
-  H160 rmd;                            // the hash160, or the ETH address (-c eth)
+  H160 rmd;                            // the hash160, the ETH address (-c eth) or the matched 20 bytes of x (-m xpoint)
 };
 
 struct AddrStats {
@@ -95,6 +106,8 @@ struct AddrCallbacks {
 // hash the kind names, then the reference's key recovery (keyhunt.cpp:2789-2937): lambda^e * key, negated when the
 // hit is the other point of the pair.  False when the hash is not a target (a bloom false positive).
 // kind KHB_ADDR_KIND_ETH (-c eth, keyhunt.cpp:2989-3002): the ETH address of key*G, the key returned unchanged.
+// kind KHB_ADDR_KIND_X | e << 2 (-m xpoint, keyhunt.cpp:3005-3062): the first 20 bytes of beta^e * x(key*G); the key
+// returned is lambda^e * key mod n (the walked key itself for e = 0), never negated; compressed = false.
 bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound* out);
 // lambda and lambda^2 mod n (keyhunt.cpp:582-583)
 const U256& endo_lambda(int e);

@@ -1,5 +1,5 @@
 // Shared pieces of the keyhunt_amd CLI (keyhunt_main.cpp: option parsing and -m bsgs;
-// keyhunt_address.cpp: -m address / -m rmd160).
+// keyhunt_address.cpp: -m address / -m rmd160 / -m xpoint).
 #pragma once
 #include <stdint.h>
 
@@ -14,8 +14,8 @@ namespace khb {
 std::string speed_line(const U256& total, uint64_t seconds);
 
 struct AddressCli {
-  int mode = 1;                       // 1 address, 3 rmd160 (keyhunt.cpp:51-57)
-  int search = 2;                     // -l (keyhunt.cpp:300: both)
+  int mode = 1;                       // 0 xpoint, 1 address, 3 rmd160 (keyhunt.cpp:51-57)
+  int search = 2;                     // -l (keyhunt.cpp:300: both); accepted and not used by -m xpoint
   bool endomorphism = false;          // -e (keyhunt.cpp:579-585)
   bool crypto_set = false;            // -c given
   bool eth = false;                   // -c eth: ETH addresses (-l is then not used for hashing)

@@ -1,4 +1,4 @@
-// keyhunt_amd -m address / -m rmd160: keyhunt.cpp main() (800-960 setup and prints, 2145-2252 stats)
+// keyhunt_amd -m address / -m rmd160 / -m xpoint: keyhunt.cpp main() (800-960 setup and prints, 2145-2252 stats)
 // and thread_process's output (writekey, keyhunt.cpp:5989-6030; writekeyeth, 6023-6051) over the libkhbsgs address scan.
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,14 +17,17 @@ namespace khb {
 
 namespace {
 
-// writekey (keyhunt.cpp:5989-6030)
-void writekey(const AddrFound& f, std::mutex& mu) {
+// writekey (keyhunt.cpp:5989-6030).  xpoint: f.rmd holds the matched bytes of x, not a hash160, and the reference's
+// writekey(false, key) prints the hash160 of the uncompressed key (keyhunt.cpp:5996-6000).
+void writekey(const AddrFound& f, std::mutex& mu, bool xpoint = false) {
   const Pt pub = mul_g(f.key);
   const std::string hexkey = f.key.hex();
   const std::string pubhex = pubkey_hex(pub, f.compressed);
-  const std::string addr = rmd_to_address(f.rmd.data());
+  H160 rmd = f.rmd;
+  if (xpoint) hash160_pub(pub, false, rmd.data());
+  const std::string addr = rmd_to_address(rmd.data());
   char rmdhex[41];
-  for (int i = 0; i < 20; ++i) snprintf(rmdhex + 2 * i, 3, "%02x", f.rmd[i]);
+  for (int i = 0; i < 20; ++i) snprintf(rmdhex + 2 * i, 3, "%02x", rmd[i]);
   std::lock_guard<std::mutex> lk(mu);
   FILE* keys = fopen("KEYFOUNDKEYFOUND.txt", "a+");
   if (keys) {
@@ -97,7 +100,8 @@ int run_address_mode(const AddressCli& o) {
   // targets (keyhunt.cpp:6300-6358, 6559-6576)
   AddrTargets T;
   std::string err;
-  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err, o.eth)) {
+  const bool xpoint = o.mode == 0;
+  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err, xpoint ? 2 : o.eth ? 1 : 0)) {
     fprintf(stderr, "[E] %s\n[E] Unenexpected error\n", err.c_str());
     return EXIT_FAILURE;
   }
@@ -105,7 +109,8 @@ int run_address_mode(const AddressCli& o) {
          (double)(20.0 * (double)T.counted / 1048576.0));
   printf("[+] Bloom filter for %llu elements.\n", (unsigned long long)T.counted);
   printf("[+] Loading data to the bloomfilter total: %.2f MB\n", (double)T.bloom.bytes / 1048576.0);
-  for (const std::string& s : T.skipped) fprintf(stderr, "[I] Ommiting invalid line %s\n", s.c_str());
+  for (const std::string& s : T.skipped)
+    fprintf(stderr, xpoint ? "[E] Omiting line : %s\n" : "[I] Ommiting invalid line %s\n", s.c_str());
   printf("[+] Sorting data ...");
   printf(" done! %llu values were loaded and sorted\n", (unsigned long long)T.table.size());
   // generator + lane offsets for one chunk of n_seq keys
@@ -113,7 +118,8 @@ int run_address_mode(const AddressCli& o) {
   const uint32_t gpl = 16;
   G.build(stride, (uint32_t)(n_seq / 1024), gpl, o.threads > 0 ? o.threads : 1);
   AddrConfig cfg;
-  cfg.search = o.eth ? KHB_SEARCH_ETH : o.search;   // -c eth: one hash per point whatever -l says
+  // -c eth: one hash per point whatever -l says; -m xpoint: -l is accepted and not used
+  cfg.search = xpoint ? KHB_SEARCH_XPOINT : o.eth ? KHB_SEARCH_ETH : o.search;
   cfg.endomorphism = o.endomorphism;
   cfg.start = start;
   cfg.end = end;
@@ -128,7 +134,7 @@ int run_address_mode(const AddressCli& o) {
   AddrStats stats;
   std::atomic<uint64_t> keys_done{0};
   AddrCallbacks cb;
-  cb.on_found = [&](const AddrFound& f) { o.eth ? writekeyeth(f, out_mu) : writekey(f, out_mu); };
+  cb.on_found = [&](const AddrFound& f) { o.eth ? writekeyeth(f, out_mu) : writekey(f, out_mu, xpoint); };
   cb.on_warning = [&](const std::string& m) {
     std::lock_guard<std::mutex> lk(out_mu);
     fprintf(stderr, "%s\n", m.c_str());
@@ -140,7 +146,7 @@ int run_address_mode(const AddressCli& o) {
     fflush(stdout);
   };
   // stats line every -s seconds (keyhunt.cpp:2145-2252): keys = groups * 1024, x6 with -e (keyhunt.cpp:2175-2180:
-  // every -l mode), else x2 for -l compress
+  // every -l mode; x3 for -m xpoint), else x2 for -l compress
   std::thread stat_th([&] {
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t sec = 0;
@@ -152,7 +158,7 @@ int run_address_mode(const AddressCli& o) {
       sec = s;
       if (o.out_seconds && s % o.out_seconds == 0) {
         U256 total(keys_done.load());
-        if (o.endomorphism) total = total * 6u;
+        if (o.endomorphism) total = total * (xpoint ? 3u : 6u);   // keyhunt.cpp:2175-2181
         else if (o.search == 1) total = total * 2u;   // also with -c eth, as the reference (keyhunt.cpp:2183-2186)
         std::lock_guard<std::mutex> lk(out_mu);
         printf("\r%s\r", speed_line(total, s).c_str());

@@ -43,7 +43,8 @@ void menu() {
   printf("-c crypto   Search for specific crypto. <btc, eth> valid only w/ -m address\n");
   printf("-f file     Specify file name with public keys (02/03 compressed or 04 uncompressed hex)\n");
   printf("-k value    Use this only with bsgs mode, k value is factor for M, more speed but more RAM use wisely\n");
-  printf("-m mode     mode of search for cryptos. (bsgs) default: bsgs\n");
+  printf("-m mode     mode of search for cryptos. (bsgs, address, rmd160, xpoint) default: bsgs\n");
+  printf("            -m xpoint: -f holds public keys or x values (64, 66 or 130 hex), searched by x\n");
   printf("-M          Matrix screen, feel like a h4x0r, but performance will dropped\n");
   printf("-n number   Use -n to set the N for the BSGS process. Bigger N more RAM needed\n");
   printf("-q          Quiet the thread output\n");
@@ -222,6 +223,7 @@ int main(int argc, char** argv) {
         if (mode < 0) { fprintf(stderr, "[E] Unknow mode value %s\n", optarg); exit(EXIT_FAILURE); }
         if (mode == 1) printf("[+] Mode address\n");
         if (mode == 3) printf("[+] Mode rmd160\n");
+        if (mode == 0) printf("[+] Mode xpoint\n");
         break;
       case 'n': str_n = optarg; break;
       case 'q': quiet = true; printf("[+] Quiet thread output\n"); break;
@@ -296,9 +298,13 @@ int main(int argc, char** argv) {
     fprintf(stderr, "[E] Stride doesn't work with BSGS\n");
     exit(EXIT_FAILURE);
   }
-  if (mode == 1 || mode == 3) {
+  if (mode == 0 || mode == 1 || mode == 3) {
     if (eth && mode == 3) {           // -c is "valid only w/ -m address"
       fprintf(stderr, "[E] -c eth is valid only with -m address (-m rmd160 searches BTC hash160 values)\n");
+      exit(EXIT_FAILURE);
+    }
+    if (eth && mode == 0) {
+      fprintf(stderr, "[E] -c eth is valid only with -m address (-m xpoint searches public-key x values)\n");
       exit(EXIT_FAILURE);
     }
     if (eth && endomorphism) {
@@ -349,7 +355,8 @@ int main(int argc, char** argv) {
     return run_address_mode(ao);
   }
   if (mode != 2) {
-    fprintf(stderr, "[E] keyhunt_amd implements -m bsgs, -m address and -m rmd160 (mode %s is not available)\n",
+    fprintf(stderr, "[E] keyhunt_amd implements -m bsgs, -m address, -m rmd160 and -m xpoint; -m minikeys and -m vanity "
+                    "remain (mode %s is not available)\n",
             kModes[mode]);
     exit(EXIT_FAILURE);
   }

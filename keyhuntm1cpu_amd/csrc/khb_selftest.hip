@@ -1,4 +1,4 @@
-// libkhbsgs.so: the self-test entry points of include/khbsgs.h (field operations, bloom probe, hash160 / ETH address) with their
+// libkhbsgs.so: the self-test entry points of include/khbsgs.h (field operations, bloom probe, hash160 / ETH address / xpoint bytes) with their
 // kernels, and the point dumps of the two walks (khb_dump_x, khb_addr_dump).  Synchronous, on slot 0.
 #include "abi.hpp"
 
@@ -57,6 +57,19 @@ __global__ void k_eth_address(const Fe* __restrict__ xy, const uint8_t* __restri
   const Fe x = xy[2 * i], y = xy[2 * i + 1];
   uint32_t h[5];
   eth_address(h, x, y);
+  uint8_t* o = out + 21 * (size_t)i;
+  for (int k = 0; k < 5; ++k)
+    for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(h[k] >> (8 * b));
+  o[20] = bloom ? (bloom_check20(bloom, g, h) ? 1 : 0) : 0;
+}
+
+// khb_hash160 kind 4: the 20 bytes -m xpoint probes for x (device/xpoint.hpp), same record as k_hash160.
+__global__ void k_x_be20(const Fe* __restrict__ xy, const uint8_t* __restrict__ bloom, BloomGeom g,
+                         uint8_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t h[5];
+  x_be20(h, xy[2 * i]);
   uint8_t* o = out + 21 * (size_t)i;
   for (int k = 0; k < 5; ++k)
     for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(h[k] >> (8 * b));
@@ -149,7 +162,7 @@ int khb_probe(khb_ctx* c, const uint8_t* xs, uint8_t* hit, uint32_t n) {
 }
 
 int khb_hash160(khb_ctx* c, int kind, const uint8_t* xy, uint8_t* out, uint32_t n) {
-  if (!c || !xy || !out || n == 0 || kind < 0 || kind > 3) return KHB_EINVAL;
+  if (!c || !xy || !out || n == 0 || kind < 0 || kind > 4) return KHB_EINVAL;
   KHB_TRY(c, hipSetDevice(c->device));
   Slot& S = c->slot[0];
   std::vector<AffPt> h;
@@ -160,7 +173,10 @@ int khb_hash160(khb_ctx* c, int kind, const uint8_t* xy, uint8_t* out, uint32_t 
   KHB_TRY(c, d.alloc(n));
   KHB_TRY(c, dout.alloc(21 * (size_t)n));
   KHB_TRY(c, hipMemcpy(d, h.data(), sizeof(AffPt) * n, hipMemcpyHostToDevice));
-  if (kind == 3)
+  if (kind == 4)
+    hipLaunchKernelGGL(k_x_be20, dim3((n + 255) / 256), dim3(256), 0, S.stream, (const Fe*)d.p, c->d_abloom, c->ageom,
+                       dout, n);
+  else if (kind == 3)
     hipLaunchKernelGGL(k_eth_address, dim3((n + 255) / 256), dim3(256), 0, S.stream, (const Fe*)d.p, c->d_abloom,
                        c->ageom, dout, n);
   else

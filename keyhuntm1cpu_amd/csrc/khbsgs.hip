@@ -264,16 +264,18 @@ namespace {
 
 // khb_submit (kind 1: -m bsgs over the level-1 bloom, kBatch groups per item on the per-group offsets) and
 // khb_addr_submit (kind 2: -m address over the address bloom, gpl groups per item, hits in the slot's h_ahits;
-// `search` selects the kernel, BTC hash160 or -c eth, and is not read for kind 1).
+// `search` selects the kernel, BTC hash160, -c eth or -m xpoint, and is not read for kind 1).
 int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, uint32_t group_begin,
                 uint32_t group_count, int search) {
   const bool bsgs = kind == 1;
   int rc = check_scan_args(c, centres, n_jobs, group_begin, group_count, bsgs);
   if (rc) return rc;
   const bool eth = !bsgs && search == KHB_SEARCH_ETH;     // exactly: no -l bits, no -e (khbsgs.h)
+  // -m xpoint: alone or with -e; with -l bits or -c eth it is KHB_EINVAL (khbsgs.h)
+  const bool xpoint = !bsgs && search >= 0 && (search & ~KHB_SEARCH_ENDOMORPHISM) == KHB_SEARCH_XPOINT;
   const bool endo = !bsgs && !eth && search >= 0 && (search & KHB_SEARCH_ENDOMORPHISM);
   if (endo) search &= ~KHB_SEARCH_ENDOMORPHISM;
-  if (!bsgs && !eth && (search < 0 || search > 2)) return KHB_EINVAL;
+  if (!bsgs && !eth && !xpoint && (search < 0 || search > 2)) return KHB_EINVAL;
   if (!(bsgs ? c->d_bloom : c->d_abloom)) return KHB_ESTATE;
   if (c->queued && c->slot[c->head].kind != kind) return KHB_EBUSY;     // a scan of the other kind is in flight
   KHB_TRY(c, hipSetDevice(c->device));
@@ -303,6 +305,8 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
     launch_bsgs(c->d_gate0 ? kScanG2 : c->d_gate1 ? kScanG1 : c->d_gate ? kScanG : kScan, blocks, S.stream, A);
   else if (eth)
     launch_addr_eth(blocks, S.stream, A);
+  else if (xpoint)
+    launch_addr_x(endo ? kAddrXE : kAddrX, blocks, S.stream, A);
   else if (endo)
     launch_addr_e(search == 0 ? kAddrUE : search == 1 ? kAddrCE : kAddrBE, blocks, S.stream, A);
   else
@@ -390,6 +394,7 @@ const char* khb_build_info(void) {
   return "abi=" KHB_STR(KHB_ABI_VERSION) " arch=gfx950 variant=" KHB_VARIANT
          " waves_per_simd=" KHB_STR(KHB_WAVES_PER_SIMD) " addr_waves_per_simd=" KHB_STR(KHB_ADDR_WAVES_PER_SIMD)
          " addr_eth_waves_per_simd=" KHB_STR(KHB_ADDR_ETH_WAVES_PER_SIMD)
+         " addr_x_waves_per_simd=" KHB_STR(KHB_ADDR_X_WAVES_PER_SIMD)
          " batch=" KHB_STR(KHB_BATCH) " gate1=" KHB_STR(KHB_GATE1) " half_stream=" KHB_STR(KHB_HALF_STREAM)
          " gate0=" KHB_STR(KHB_GATE0) " defines=" KHB_BUILD_DEFINES " compiler=" __clang_version__;
 }

@@ -1,5 +1,5 @@
 // Device side of libkhbsgs (gfx950): the giant-step walk and its kernel k_giant_scan<MODE>, shared by
-// the translation units that instantiate it (k_bsgs.hip: -m bsgs scan / x dump; k_addr*.hip: -m address;
+// the translation units that instantiate it (k_bsgs.hip: -m bsgs scan / x dump; k_addr*.hip: -m address, -m xpoint;
 // k_baby.hip: baby-step tables) and by khbsgs.hip (types, self-test kernels, the C ABI).  Splitting the
 // instances over translation units lets `make -j` compile them in parallel.
 //
@@ -124,6 +124,7 @@ void launch_bsgs(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& 
 void launch_addr(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);   // kAddrU, kAddrC, kAddrB, kAddrDump
 void launch_addr_e(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrUE, kAddrCE, kAddrBE
 void launch_addr_eth(uint32_t blocks, hipStream_t stream, const ScanArgs& A);         // kAddrEth
+void launch_addr_x(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrX, kAddrXE
 void launch_baby(uint32_t blocks, hipStream_t stream, const ScanArgs& A);             // kBaby
 
 }  // namespace khbk

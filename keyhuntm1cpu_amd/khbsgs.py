@@ -62,6 +62,7 @@ KHB_ABI_VERSION = 7
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
 FIELD_OP_RAW = 0x100                                             # include/khbsgs.h KHB_FIELD_OP_RAW
 SEARCH_ENDOMORPHISM, SEARCH_ETH, ADDR_KIND_ETH = 4, 8, 16        # include/khbsgs.h KHB_SEARCH_*, KHB_ADDR_KIND_ETH
+SEARCH_XPOINT, ADDR_KIND_X = 16, 32                              # KHB_SEARCH_XPOINT, KHB_ADDR_KIND_X (| e << 2)
 
 
 def lib(path: str | None = None) -> C.CDLL:
@@ -342,7 +343,7 @@ class Engine:
 
     def addr_scan(self, centres: bytes, group_begin: int, group_count: int, search: int = 2, cap: int = 1 << 18):
         """Bloom hits [(job, group, t, kind)] of -m address over group_count groups of each job (search: 0/1/2,
-        | SEARCH_ENDOMORPHISM, or SEARCH_ETH)."""
+        | SEARCH_ENDOMORPHISM, SEARCH_ETH, or SEARCH_XPOINT optionally | SEARCH_ENDOMORPHISM)."""
         hits = (AddrHit * cap)()
         st = Stats()
         _check(self.L.khb_addr_scan(self.h, centres, len(centres) // 64, group_begin, group_count, search, hits, cap,
@@ -356,7 +357,8 @@ class Engine:
         return out.raw
 
     def hash160(self, kind: int, xy: bytes) -> list[tuple[bytes, int]]:
-        """[(hash160, bloom bit)] of each x||y point for kind 0/1 (compressed 02/03) or 2; kind 3: its ETH address."""
+        """[(hash160, bloom bit)] of each x||y point for kind 0/1 (compressed 02/03) or 2; kind 3: its ETH address;
+        kind 4: the first 20 bytes of x (-m xpoint)."""
         n = len(xy) // 64
         out = C.create_string_buffer(21 * n)
         _check(self.L.khb_hash160(self.h, kind, xy, out, n), self.h, self.L)

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 8                 # include/khhost.h
+KHH_ABI_VERSION = 9                 # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
 KHH_RESIDENT_INFO = 8
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
@@ -99,6 +99,10 @@ def lib() -> C.CDLL:
                                    C.c_size_t]
         L.khh_addr_new_eth.restype = C.c_void_p
         L.khh_addr_new_eth.argtypes = L.khh_addr_new.argtypes
+        L.khh_addr_new_xpoint.restype = C.c_void_p
+        L.khh_addr_new_xpoint.argtypes = L.khh_addr_new.argtypes
+        L.khh_addr_counted.restype = C.c_uint64
+        L.khh_addr_counted.argtypes = [C.c_void_p]
         L.khh_addr_free.argtypes = [C.c_void_p]
         L.khh_addr_skipped.restype = C.c_uint64
         L.khh_addr_skipped.argtypes = [C.c_void_p]
@@ -467,22 +471,32 @@ def eth_address(xy: bytes) -> bytes:
 
 class Addr:
     """-m address targets (a target file's text) + generator for chunks of n_seq keys.  crypto="eth": the text is
-    read as -c eth reads it (ETH addresses) and the handle is searched with KHB_SEARCH_ETH."""
+    read as -c eth reads it (ETH addresses) and the handle is searched with KHB_SEARCH_ETH.  mode="xpoint": the text
+    is read as -m xpoint reads it (x values and public keys) and the handle is searched with KHB_SEARCH_XPOINT."""
 
     def __init__(self, text: str, n_seq: int = 1 << 32, stride: int = 1, gpl: int = 16, bloom_multiplier: int = 1,
-                 threads: int = 0, crypto: str = "btc"):
+                 threads: int = 0, crypto: str = "btc", mode: str = "address"):
         if crypto not in ("btc", "eth"):
             raise ValueError("crypto: btc or eth")
+        if mode not in ("address", "xpoint"):
+            raise ValueError("mode: address or xpoint")
+        if mode == "xpoint" and crypto == "eth":
+            raise ValueError("mode xpoint has no crypto eth")
         err = C.create_string_buffer(256)
-        new = lib().khh_addr_new_eth if crypto == "eth" else lib().khh_addr_new
+        new = (lib().khh_addr_new_xpoint if mode == "xpoint"
+               else lib().khh_addr_new_eth if crypto == "eth" else lib().khh_addr_new)
         self.h = new(text.encode(), bloom_multiplier, _b32(stride), n_seq, gpl, threads, err, 256)
         if not self.h:
             raise KhhError(err.value.decode())
-        self.n_seq, self.stride, self.crypto = n_seq, stride, crypto
+        self.n_seq, self.stride, self.crypto, self.mode = n_seq, stride, crypto, mode
 
     def skipped(self) -> int:
         """Lines the loader omitted as invalid."""
         return int(lib().khh_addr_skipped(self.h))
+
+    def counted(self) -> int:
+        """Lines the loader counted (they size the bloom)."""
+        return int(lib().khh_addr_counted(self.h))
 
     def close(self) -> None:
         if self.h:
@@ -542,7 +556,8 @@ class Addr:
     def search(self, start: int, end: int, search: int = 2, devices=(0,), lanes: int = 0, max_chunks: int = 0,
                random_chunks: bool = False, cap: int = 4096):
         """Found [(key, compressed, rmd160)] in discovery order, plus stats.  search | 4 (KHB_SEARCH_ENDOMORPHISM)
-        is -e; search = 8 (KHB_SEARCH_ETH) on a crypto="eth" handle gives (key, False, address)."""
+        is -e; search = 8 (KHB_SEARCH_ETH) on a crypto="eth" handle gives (key, False, address); search = 16
+        (KHB_SEARCH_XPOINT), alone or | 4, on a mode="xpoint" handle gives (key, False, first 20 bytes of x)."""
         keys = C.create_string_buffer(32 * cap)
         comp = C.create_string_buffer(cap)
         rmd = C.create_string_buffer(20 * cap)

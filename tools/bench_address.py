@@ -3,9 +3,12 @@ MI355X, sequential chunks of -n keys from 2^70 (puzzle #71's range), reported as
 VALU roofline of the hash path.  Prints one JSON line.
 
 Usage: python tools/bench_address.py [--search 2] [--chunks 24] [--n 0x100000000] [--crypto btc|eth]
+       [--mode address|xpoint] [--endo]
 (24 chunks of 2^32 keys = three launches of eight work items per lane, two queued at a time.)
 --crypto eth: keyhunt -m address -c eth -f tests/1to32.eth over the same range and chunking (--search is not read:
 one Keccak-256 per key).
+--mode xpoint: keyhunt -m xpoint -f tests/1to63_65.txt over the same range and chunking (--search is not read: no
+hash, the first 20 bytes of x probed); --endo adds -e (x, beta*x and beta^2*x per key; keys counted once).
 """
 from __future__ import annotations
 
@@ -35,6 +38,11 @@ OPS_ETH = KECCAK_F + 16 + EC_PER_KEY
 # 8-chunk launch, profiles/r02w/addr_valu_counter_collection.csv: 4.968e12 wave-instr x 64 / 2^35 keys;
 # VALUBusy 101.5 %: the kernel is at the VALU issue ceiling).
 EXEC_PER_KEY = {2: 9253.4}
+# -m xpoint: no hash.  The x-only walk is ~2.5 field multiplies per key (two steps share the inverse's three) at ~150
+# VALU each, + 5 byte swaps and two XXH64 of 20 bytes (~60 32-bit operations each with the 64-bit multiplies split).
+# -e adds two multiplies by beta, their canonicalisations and two more probes.
+OPS_X = 375 + 5 + 120
+OPS_XE = OPS_X + 2 * (150 + 20) + 2 * 125
 PEAK_T = 68.2   # measured v_add_u32 / v_xor issue, 111 lane-ops/clk/CU x 256 CU x 2.4 GHz (profiles/r01_intops2.txt)
 
 
@@ -45,11 +53,18 @@ def main() -> None:
     ap.add_argument("--n", type=lambda s: int(s, 0), default=1 << 32)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--crypto", choices=["btc", "eth"], default="btc", help="eth: -c eth over tests/1to32.eth")
+    ap.add_argument("--mode", choices=["address", "xpoint"], default="address", help="xpoint: -m xpoint over tests/1to63_65.txt")
+    ap.add_argument("--endo", action="store_true", help="-e (with --mode xpoint)")
     args = ap.parse_args()
     eth = args.crypto == "eth"
-    search = 8 if eth else args.search           # KHB_SEARCH_ETH
-    ops = OPS_ETH if eth else OPS[args.search]
-    targets = "1to32.eth" if eth else "unsolvedpuzzles.rmd"
+    xpoint = args.mode == "xpoint"
+    if xpoint and eth:
+        ap.error("--mode xpoint has no --crypto eth")
+    if args.endo and not xpoint:
+        ap.error("--endo is measured with --mode xpoint")
+    search = (16 | (4 if args.endo else 0)) if xpoint else 8 if eth else args.search   # KHB_SEARCH_XPOINT, _ETH
+    ops = (OPS_XE if args.endo else OPS_X) if xpoint else OPS_ETH if eth else OPS[args.search]
+    targets = "1to63_65.txt" if xpoint else "1to32.eth" if eth else "unsolvedpuzzles.rmd"
     import torch  # noqa: F401  (share torch's HIP runtime, as bench.py)
     from keyhuntm1cpu_amd import khbsgs, khhost
     with open(os.path.join(REPO, "tests", "golden", "address", targets)) as f:
@@ -57,7 +72,7 @@ def main() -> None:
     build = khbsgs.build_info()                  # the line names the kernel build it measured, as bench.py's does
     build["path"] = os.path.relpath(build["path"], REPO)
     t0 = time.time()
-    A = khhost.Addr(text, n_seq=args.n, threads=16, crypto=args.crypto)
+    A = khhost.Addr(text, n_seq=args.n, threads=16, crypto=args.crypto, mode=args.mode)
     t_build = time.time() - t0
     start = 1 << 70
     if args.warmup:
@@ -71,15 +86,19 @@ def main() -> None:
     kern = st["kernel_s"] / max(1, st["launches"])
     achieved = ops * keys / st["kernel_s"] / 1e12
     out = {
-        "metric": "Mkeys/s (-m address, keys hashed and probed per second)",
+        "metric": "Mkeys/s (-m xpoint, keys walked and probed per second)" if xpoint else
+                  "Mkeys/s (-m address, keys hashed and probed per second)",
         "value": round(rate / 1e6, 2),
         "unit": "Mkeys/s",
         "n_gpus": 1,
         "keys": keys,
         "seconds": round(dt, 3),
-        "search": "eth" if eth else ["uncompress", "compress", "both"][args.search],
-        "reference_keys_per_s": round(rate * (2 if args.search == 1 and not eth else 1) / 1e6, 2),
-        "config": {"workload": "-m address -c eth -f tests/1to32.eth -b 71" if eth else
+        "search": ("xpoint -e" if args.endo else "xpoint") if xpoint else
+                  "eth" if eth else ["uncompress", "compress", "both"][args.search],
+        "reference_keys_per_s": round(rate * (3 if args.endo else 2 if args.search == 1 and not eth and not xpoint
+                                              else 1) / 1e6, 2),
+        "config": {"workload": "-m xpoint -f tests/1to63_65.txt -b 71" + (" -e" if args.endo else "") if xpoint else
+                               "-m address -c eth -f tests/1to32.eth -b 71" if eth else
                                "-m address -f tests/unsolvedpuzzles.rmd -b 71 (BASELINE configs[4])",
                    "build": build,
                    "targets": len(A.table()), "n_seq": hex(args.n), "chunks": st["chunks"],
@@ -89,10 +108,10 @@ def main() -> None:
                      "frac": round(achieved / PEAK_T, 4), "ops_per_key": ops,
                      "achieved_wall": round(ops * rate / 1e12, 3),
                      "frac_wall": round(ops * rate / 1e12 / PEAK_T, 4),
-                     "kernel": "k_giant_scan<address>", "kernel_ms_avg": round(kern * 1e3, 3),
+                     "kernel": "k_giant_scan<xpoint>" if xpoint else "k_giant_scan<address>", "kernel_ms_avg": round(kern * 1e3, 3),
                      "shader_mhz": round(st["shader_mhz"], 1)},
     }
-    if not eth and args.search in EXEC_PER_KEY:
+    if not eth and not xpoint and args.search in EXEC_PER_KEY:
         e = EXEC_PER_KEY[args.search]
         out["roofline"]["executed"] = {
             "valu_lane_instr_per_key": e, "valu_busy_pct": 101.5,
