@@ -120,6 +120,7 @@ uint64_t ora_bsgs_bench(const ora_bsgs* c, const ora_point* target, const ora_u2
 void ora_sha256(const uint8_t* msg, size_t len, uint8_t out[32]);
 void ora_ripemd160(const uint8_t* msg, size_t len, uint8_t out[20]);
 void ora_hash160(const uint8_t* msg, size_t len, uint8_t out[20]);
+void ora_hash160_many(const uint8_t* msgs, size_t len, size_t n, uint8_t* out);   /* ora_hash160 of n messages */
 void ora_pub_hash160(const ora_point* p, int compressed, uint8_t out[20]);   /* SECP256K1.cpp:671-705 */
 void ora_x_hash160(uint8_t prefix, const ora_u256* x, uint8_t out[20]);     /* SECP256K1.cpp:707-789 */
 int  ora_b58decode(const char* s, uint8_t* bin, size_t binsz, size_t* outsz); /* base58.c:39-112 */
@@ -134,6 +135,7 @@ void      ora_addr_free(ora_addr* A);
 uint64_t  ora_addr_count(const ora_addr* A);
 const uint8_t* ora_addr_table(const ora_addr* A);
 const ora_bloom* ora_addr_bloom(const ora_addr* A);
+void      ora_addr_bloom_check_many(const ora_addr* A, const uint8_t* v20, size_t n, uint8_t* out);
 int       ora_addr_searchbinary(const ora_addr* A, const uint8_t data[20]);   /* keyhunt.cpp:2311-2335 */
 /* init_generator (keyhunt.cpp:4386-4399): Gn[i] = (i+1)*stride*G, _2Gn = 1024*stride*G */
 ora_addr_gen* ora_addr_gen_new(const ora_u256* stride);

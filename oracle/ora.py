@@ -108,6 +108,7 @@ def lib() -> C.CDLL:
         L.ora_sha256.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
         L.ora_ripemd160.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
         L.ora_hash160.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
+        L.ora_hash160_many.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p]
         L.ora_pub_hash160.argtypes = [P(Point), C.c_int, C.c_char_p]
         L.ora_x_hash160.argtypes = [C.c_uint8, P(U256), C.c_char_p]
         L.ora_b58decode.restype = C.c_int
@@ -122,6 +123,7 @@ def lib() -> C.CDLL:
         L.ora_addr_table.argtypes = [C.c_void_p]
         L.ora_addr_bloom.restype = P(Bloom)
         L.ora_addr_bloom.argtypes = [C.c_void_p]
+        L.ora_addr_bloom_check_many.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p]
         L.ora_addr_searchbinary.restype = C.c_int
         L.ora_addr_searchbinary.argtypes = [C.c_void_p, C.c_char_p]
         L.ora_addr_gen_new.restype = C.c_void_p
@@ -296,6 +298,14 @@ def hash160(data: bytes) -> bytes:
     return out.raw
 
 
+def hash160_many(msgs: bytes, length: int) -> bytes:
+    """hash160 of each of the len(msgs) // length messages of `length` bytes laid back to back, 20 bytes each."""
+    n = len(msgs) // length
+    out = C.create_string_buffer(20 * n)
+    lib().ora_hash160_many(msgs, length, n, out)
+    return out.raw
+
+
 def pub_hash160(p: Point, compressed: bool) -> bytes:
     out = C.create_string_buffer(20)
     lib().ora_pub_hash160(C.byref(p), 1 if compressed else 0, out)
@@ -355,6 +365,13 @@ class AddrTable:
 
     def bloom_check(self, h20: bytes) -> bool:
         return bool(lib().ora_bloom_check(lib().ora_addr_bloom(self.h), h20, 20))
+
+    def bloom_check_many(self, v20: bytes) -> bytes:
+        """bloom_check of each 20-byte value of v20: one byte 0 / 1 per value."""
+        n = len(v20) // 20
+        out = C.create_string_buffer(n)
+        lib().ora_addr_bloom_check_many(self.h, v20, n, out)
+        return out.raw[:n]
 
     def searchbinary(self, h20: bytes) -> bool:
         return bool(lib().ora_addr_searchbinary(self.h, h20))

@@ -146,6 +146,11 @@ void ora_hash160(const uint8_t* msg, size_t len, uint8_t out[20]) {
   ora_ripemd160(d, 32, out);
 }
 
+/* n messages of len bytes each, back to back: out + 20 i = ora_hash160 of message i (one call for a test's batch) */
+void ora_hash160_many(const uint8_t* msgs, size_t len, size_t n, uint8_t* out) {
+  for (size_t i = 0; i < n; ++i) ora_hash160(msgs + i * len, len, out + 20 * i);
+}
+
 /* GetHash160(P2PKH, compressed, P) SECP256K1.cpp:671-705 */
 void ora_pub_hash160(const ora_point* p, int compressed, uint8_t out[20]) {
   uint8_t b[65];
@@ -333,6 +338,10 @@ void ora_addr_free(ora_addr* A) {
 uint64_t ora_addr_count(const ora_addr* A) { return A->n; }
 const uint8_t* ora_addr_table(const ora_addr* A) { return A->table; }
 const ora_bloom* ora_addr_bloom(const ora_addr* A) { return &A->bloom; }
+/* out[i] = ora_bloom_check of the 20-byte value i in the target bloom */
+void ora_addr_bloom_check_many(const ora_addr* A, const uint8_t* v20, size_t n, uint8_t* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = (uint8_t)(ora_bloom_check(&A->bloom, v20 + 20 * i, 20) != 0);
+}
 
 /* searchbinary keyhunt.cpp:2311-2335 */
 int ora_addr_searchbinary(const ora_addr* A, const uint8_t data[20]) {

@@ -9,7 +9,8 @@ Three things live here, all on Python integers:
     branch a given operand needs.  The model is never the expected value of a test: it chooses operands
     and certifies that each one arithmetically requires the branch it is aimed at;
   * planting: start points such that a chosen step of a chosen group of the walk lands on a chosen point,
-    the reference's rule for a group's centre, and a reference of one -m address group from a centre.
+    the reference's rule for a group's centre, a reference of one -m address group from a centre (degenerate
+    groups included) and of one launch of a job as the library splits it over lanes.
 """
 from __future__ import annotations
 
@@ -435,27 +436,76 @@ def ref_centre(ora, bs, start, g: int):
     return ora.add_direct(sp, ora.Point.of(*group_offset(ora, bs, g)))
 
 
+def add_direct_ref(p1, p2, inverse=None):
+    """AddDirect(p1, p2) (SECP256K1.cpp:242-265) on integers: s = (p2.y - p1.y) * inverse, x = s^2 - p1.x - p2.x,
+    y = (p2.x - x) * s - p2.y, with inverse = ModInv(p2.x - p1.x) unless given (a batch's inverse), and ModInv(0) = 0.
+    Returns (point, collapsed): collapsed when p2.x == p1.x.  The operands need not be on the curve."""
+    dx = (p2[0] - p1[0]) % P
+    if inverse is None:
+        inverse = inv(dx)
+    s = (p2[1] - p1[1]) * inverse % P
+    x = (s * s - p1[0] - p2[0]) % P
+    return (x, ((p2[0] - x) * s - p2[1]) % P), dx == 0
+
+
 def addr_group_ref(centre, gn: list):
     """One -m address group from its centre C with the table Gn[0..511], _2Gn (keyhunt.cpp:2586-2711):
-    pts[t] = C - Gn[511 - t] (t < 512), C (t = 512), C + Gn[t - 513] (t > 512) as x||y, and the next centre
-    C + _2Gn.  Plain chord additions (C is never +-Gn[i]) with the 513 inverses from one batch inversion."""
+    pts[t] = C - Gn[511 - t] (t < 512), C (t = 512), C + Gn[t - 513] (t > 512) as x||y, the next centre C + _2Gn
+    (AddDirect's formulas with the batch's inverse, keyhunt.cpp:3986-3999) and whether the group is degenerate.
+    The 513 inverses come from one batch inversion, so they are all 0 when any dx is 0 (C = +-Gn[k] or +-_2Gn:
+    IntGroup.cpp:36-58 with ModInv(0) = 0), and y follows the walk's own formulas, which give the reference's
+    value with such an inverse too: (x - Gn.x) * s' + Gn.y with s' = (Gn.y + C.y) * inv for C - Gn[i]
+    (keyhunt.cpp:2628-2641), (Gn.x - x) * s - Gn.y with s = (Gn.y - C.y) * inv for C + Gn[i] (2611-2624).  C need
+    not be on the curve (the centre after a degenerate group is not)."""
     cx, cy = centre
     dx = [(g[0] - cx) % P for g in gn]
-    assert all(dx)
-    pre = [1]
-    for d in dx:
-        pre.append(pre[-1] * d % P)
-    acc = inv(pre[-1])
+    degenerate = not all(dx)
     inverse = [0] * len(dx)
-    for i in range(len(dx) - 1, -1, -1):
-        inverse[i] = acc * pre[i] % P
-        acc = acc * dx[i] % P
+    if not degenerate:
+        pre = [1]
+        for d in dx:
+            pre.append(pre[-1] * d % P)
+        acc = inv(pre[-1])
+        for i in range(len(dx) - 1, -1, -1):
+            inverse[i] = acc * pre[i] % P
+            acc = acc * dx[i] % P
 
-    def chord(i, sign):
-        gx, gy = gn[i][0], gn[i][1] if sign > 0 else P - gn[i][1]
-        s = (gy - cy) * inverse[i] % P
+    def minus(i):
+        gx, gy = gn[i]
+        s = (gy + cy) * inverse[i] % P
         x = (s * s - cx - gx) % P
-        return x, (s * (cx - x) - cy) % P
+        return x, ((x - gx) * s + gy) % P
 
-    out = [chord(HALF - 1 - t, -1) for t in range(HALF)] + [centre] + [chord(t, +1) for t in range(HALF - 1)]
-    return b"".join(be64(p) for p in out), chord(HALF, +1)
+    def plus(i):
+        return add_direct_ref(centre, gn[i], inverse[i])[0]
+
+    out = [minus(HALF - 1 - t) for t in range(HALF)] + [centre] + [plus(t) for t in range(HALF - 1)]
+    return b"".join(be64(p) for p in out), plus(HALF), degenerate
+
+
+def addr_lanes_ref(start, gn: list, offs: list, gpl: int, ngroups: int, cache: dict | None = None):
+    """One launch of one -m address job as the library lays it out (scan_kernels.hpp, scan_group): lane m walks
+    groups [m * gpl, min((m + 1) * gpl, ngroups)) from AddDirect(start, offs[m]) with ModInv(0) = 0 (lane 0 from
+    start itself; offs[m] = (m * gpl) * _2Gn), each group handing its next centre on to the following one.  Returns
+    (x||y of the ngroups groups, the set of degenerate records the kernel emits): (m * gpl) | 0x80000000 for a lane
+    add that collapses (start = +-offs[m]), g for every degenerate group.  Centres that are no longer on the curve
+    are integers like any other.  cache: {centre: addr_group_ref(centre, gn)}, shared between calls with one gn."""
+    xy, records = [], set()
+    for m in range((ngroups + gpl - 1) // gpl):
+        c = start
+        if m:
+            c, collapsed = add_direct_ref(start, offs[m])
+            if collapsed:
+                records.add((m * gpl) | 0x80000000)
+        for g in range(m * gpl, min((m + 1) * gpl, ngroups)):
+            if cache is None:
+                ref = addr_group_ref(c, gn)
+            else:
+                ref = cache.get(c)
+                if ref is None:
+                    ref = cache[c] = addr_group_ref(c, gn)
+            xy.append(ref[0])
+            if ref[2]:
+                records.add(g)
+            c = ref[1]
+    return b"".join(xy), records

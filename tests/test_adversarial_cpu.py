@@ -179,9 +179,130 @@ def test_addr_group_reference_matches_oracle(ora):
         for key in (0x123456789ABCDEF0123, adv.N - 5000):
             _, _, ref = gen.group(O, key, 2, want_xy=True)
             centre = ora.pubkey(key + 512).xy()
-            got, nxt = adv.addr_group_ref(centre, gn)
-            assert got == ref
+            got, nxt, degenerate = adv.addr_group_ref(centre, gn)
+            assert got == ref and not degenerate
             assert nxt == ora.pubkey(key + 512 + 1024).xy()
     finally:
         gen.close()
         O.close()
+
+
+# ------------------------------------------------------------ the -m address model's degenerate branch
+
+@pytest.fixture(scope="module")
+def addr_gen(ora):
+    gen = ora.AddrGen(1)
+    O = ora.AddrTable("00" * 20 + "\n")
+    yield gen, O, adv.table_points(gen.table())
+    gen.close()
+    O.close()
+
+
+SPECIAL_K = (0, 1, 2, 509, 510, 511)
+
+
+def _degenerate_keys():
+    """[(first key of the group, its centre as a signed multiple of G)]: centre = (key + 512) * G on +-_2Gn and on
+    +-Gn[k]; the oracle takes keys >= n as they are."""
+    rows = [(512, 1024), (adv.N - 1536, -1024)]
+    for k in SPECIAL_K:
+        rows += [(adv.N - k - 513, -(k + 1)), (adv.N + k - 511, k + 1)]
+    return rows
+
+
+def test_addr_group_reference_matches_oracle_on_degenerate_centres(ora, addr_gen):
+    """Centres on +-Gn[k] and +-_2Gn: every inverse of the batch is 0, and the model's x||y equal the oracle's group
+    byte for byte on all 1024 points; the centre is the only true point of such a group.  Ordinary centres
+    (near n as well) are not degenerate and unchanged."""
+    gen, O, gn = addr_gen
+    for key, c in _degenerate_keys():
+        centre = ora.pubkey(c % adv.N).xy()
+        row = gn[512] if abs(c) == 1024 else gn[abs(c) - 1]
+        assert centre == (row if c > 0 else adv.neg(row))
+        _, _, ref = gen.group(O, key, 2, want_xy=True)
+        got, nxt, degenerate = adv.addr_group_ref(centre, gn)
+        assert degenerate and got == ref, (key, c)
+        assert got[64 * 512:64 * 513] == adv.be64(centre)
+        # every other point: s = 0, so x = -(C.x + Gn.x) and y = +-Gn.y, and the next centre likewise
+        assert got[:64] == adv.be64(((-centre[0] - gn[511][0]) % P, gn[511][1]))
+        assert got[-64:] == adv.be64(((-centre[0] - gn[510][0]) % P, P - gn[510][1]))
+        assert nxt == ((-centre[0] - gn[512][0]) % P, P - gn[512][1])
+        true = sum(got[64 * t:64 * t + 64] == ora.pubkey((key + t) % adv.N).be64() for t in range(1024)
+                   if (key + t) % adv.N)
+        assert true == 1
+    for key in (0x123456789ABCDEF0123, 1, 513, adv.N - 5000, adv.N - 1537, adv.N - 1535):
+        _, _, ref = gen.group(O, key, 2, want_xy=True)
+        got, nxt, degenerate = adv.addr_group_ref(ora.pubkey(key + 512).xy(), gn)
+        assert got == ref and not degenerate and nxt == ora.pubkey((key + 1536) % adv.N).xy(), key
+
+
+def test_add_direct_reference_matches_oracle(ora, addr_gen):
+    """AddDirect on integers against the oracle's: ordinary operands, and p2.x == p1.x (ModInv(0) = 0), which is
+    the collapsed lane-offset add (start = +-offs[m]) and the next-centre add of a group centred on +-_2Gn."""
+    _, _, gn = addr_gen
+    g2 = gn[512]
+    a, b = ora.pubkey(0xABCDEF).xy(), ora.pubkey(0x1234567).xy()
+    cases = [(a, b, False), (a, a, True), (a, adv.neg(a), True), (g2, g2, True), (adv.neg(g2), g2, True),
+             (ora.pubkey(3 * 1024).xy(), ora.pubkey(3 * 1024).xy(), True),
+             (ora.negation(ora.pubkey(4096)).xy(), ora.pubkey(4096).xy(), True),
+             ((5, 7), b, False)]                                        # an operand off the curve
+    for p1, p2, collapsed in cases:
+        got, c = adv.add_direct_ref(p1, p2)
+        assert c == collapsed
+        assert got == ora.add_direct(ora.Point.of(*p1), ora.Point.of(*p2)).xy(), (p1, p2)
+        if collapsed:
+            assert got == ((-p1[0] - p2[0]) % P, P - p2[1])
+    # the next centre of a group on +-_2Gn is that add with the batch's inverse, 0
+    for c in (g2, adv.neg(g2)):
+        assert adv.addr_group_ref(c, gn)[1] == ora.add_direct(ora.Point.of(*c), ora.Point.of(*g2)).xy()
+    assert adv.add_direct_ref(a, b, 0)[0] == ((-a[0] - b[0]) % P, P - b[1])
+
+
+def _offs(ora, gpl: int, n: int) -> list:
+    return [None] + [ora.pubkey(m * gpl * 1024).xy() for m in range(1, n)]
+
+
+@pytest.mark.parametrize("gpl", [1, 4])
+def test_addr_lanes_reference(ora, addr_gen, gpl):
+    """addr_lanes_ref on an ordinary start equals the oracle's groups walked one by one (6 groups: a short last lane
+    at 4 groups per lane) and reports nothing; on starts that collapse it is pinned against the oracle group by
+    group wherever a group's centre is still the key's own point."""
+    gen, O, gn = addr_gen
+    base = 0x7123456789ABCDEF
+    offs = _offs(ora, gpl, 6)
+    cache = {}
+    xy, rec = adv.addr_lanes_ref(ora.pubkey(base + 512).xy(), gn, offs, gpl, 6, cache)
+    assert rec == set() and len(cache) == 6
+    for g in range(6):
+        assert xy[65536 * g:65536 * (g + 1)] == gen.group(O, base + 1024 * g, 2, want_xy=True)[2], g
+    assert adv.addr_lanes_ref(ora.pubkey(base + 512).xy(), gn, offs, gpl, 6) == (xy, rec)
+    # group 0 on Gn[0]: reported; at one group per lane the later lanes restart from exact offsets, at four the
+    # chain goes on from a centre off the curve and no later group of the lane is the oracle's
+    key = adv.N - 511
+    xy, rec = adv.addr_lanes_ref(gn[0], gn, offs, gpl, 4)
+    assert rec == {0}
+    exact = [xy[65536 * g:65536 * (g + 1)] == gen.group(O, key + 1024 * g, 2, want_xy=True)[2] for g in range(4)]
+    assert exact == ([True] * 4 if gpl == 1 else [True, False, False, False])
+    centres = [(int.from_bytes(xy[65536 * g + 32768:][:32], "big"), int.from_bytes(xy[65536 * g + 32800:][:32], "big"))
+               for g in range(4)]
+    assert [adv.on_curve(c) for c in centres] == ([True] * 4 if gpl == 1 else [True, False, False, False])
+    # start = offs[1]: the lane add collapses (m * gpl | 0x80000000) and lane 1 walks from (-2x, -y)
+    n = 2 * gpl
+    xy, rec = adv.addr_lanes_ref(offs[1], gn, offs, gpl, n)
+    assert 0x80000000 | gpl in rec and rec - {0x80000000 | gpl} == ({0} if gpl == 1 else set())
+    o = offs[1]
+    assert xy[65536 * gpl + 32768:][:64] == adv.be64(((-2 * o[0]) % P, P - o[1]))
+    xy2, rec2 = adv.addr_lanes_ref(adv.neg(offs[1]), gn, offs, gpl, n)
+    assert 0x80000000 | gpl in rec2
+    assert xy2[65536 * gpl + 32768:][:64] == adv.be64(((-2 * o[0]) % P, P - o[1]))
+
+
+def test_oracle_batch_helpers(ora):
+    """hash160_many and AddrTable.bloom_check_many are loops over the single calls."""
+    rng = random.Random(4)
+    msgs = [bytes(rng.randrange(256) for _ in range(33)) for _ in range(50)]
+    assert ora.hash160_many(b"".join(msgs), 33) == b"".join(ora.hash160(m) for m in msgs)
+    h = [ora.hash160(m) for m in msgs]
+    with ora.AddrTable("\n".join(x.hex() for x in h[::2]) + "\n") as O:
+        got = O.bloom_check_many(b"".join(h))
+        assert list(got) == [1 if O.bloom_check(x) else 0 for x in h] and all(got[::2]) and not all(got)

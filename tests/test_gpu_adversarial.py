@@ -361,7 +361,7 @@ def test_addr_dump_on_planted_points(eng, ora, cls, gpl):
         if (cls, k) not in _addr_refs:
             ref, c = b"", centre
             for _ in range(NGROUPS):
-                xy, c = adv.addr_group_ref(c, gn)
+                xy, c, _ = adv.addr_group_ref(c, gn)
                 ref += xy
             _addr_refs[cls, k] = ref
         ref = _addr_refs[cls, k]
