@@ -6,12 +6,12 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
-#include <deque>
 #include <thread>
 
 #include "../../../include/khbsgs.h"
 #include "../device/hash160.hpp"
 #include "../device/keccak.hpp"
+#include "pipeline.hpp"
 
 namespace khb {
 
@@ -150,12 +150,12 @@ std::string rmd_to_address(const uint8_t rmd[20]) {
 }
 
 // ------------------------------------------------------------------------------- targets
-static void trim(char* s) {
+// The line as a C string (up to an embedded NUL) without its leading and trailing whitespace.
+static std::string trimmed(const std::string& line) {
   const char* seps = " \t\n\r";
-  size_t n = strlen(s);
-  while (n && strchr(seps, s[n - 1])) s[--n] = 0;
-  const size_t k = strspn(s, seps);
-  if (k) memmove(s, s + k, n + 1 - k);
+  const std::string s(line.c_str());
+  const size_t b = s.find_first_not_of(seps);
+  return b == std::string::npos ? std::string() : s.substr(b, s.find_last_not_of(seps) - b + 1);
 }
 
 static bool all_b58(const char* s) {
@@ -175,7 +175,7 @@ static bool all_hex(const char* s) {
 static int hexv(char c) { return c <= '9' ? c - '0' : (c | 32) - 'a' + 10; }
 
 // Split like fgets(aux, size, f): a line longer than size - 1 characters continues in the next read.
-static std::vector<std::string> fgets_lines(const std::string& text, size_t size = 100) {
+static std::vector<std::string> fgets_lines(const std::string& text, size_t size) {
   std::vector<std::string> out;
   size_t p = 0;
   while (p < text.size()) {
@@ -188,135 +188,67 @@ static std::vector<std::string> fgets_lines(const std::string& text, size_t size
   return out;
 }
 
-bool AddrTargets::load_text(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err) {
-  T = AddrTargets();
-  const std::vector<std::string> lines = fgets_lines(text);
-  char aux[128];
-  for (const std::string& l : lines) {
-    snprintf(aux, sizeof aux, "%s", l.c_str());
-    trim(aux);
-    if (strlen(aux) > 20) ++T.counted;
+static void hex20(const char* hex, H160& h) {
+  for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(hex[2 * k]) * 16 + hexv(hex[2 * k + 1]));
+}
+
+// One trimmed target line to its 20 bytes; false: "Ommiting invalid line".
+static bool line_h160(TargetKind kind, const std::string& aux, H160& h) {
+  const size_t r = aux.size();
+  if (kind == kTargetsXpoint) {
+    // stringtokenizer (util.c:67-84): trim "\t\n\r :", then the first strtok(" \t:") token: 64 hex = x, 66 hex = a
+    // compressed key (prefix unchecked), 130 hex = 04 || x || y: x[0..19] for bloom and table (see address_host.hpp)
+    const size_t t0 = std::min(aux.find_first_not_of(" \t:"), r);
+    const std::string token = aux.substr(t0, aux.find_first_of(" \t:", t0) - t0);
+    const size_t n = token.size();
+    if ((n != 64 && n != 66 && n != 130) || !all_hex(token.c_str())) return false;
+    hex20(token.c_str() + (n == 64 ? 0 : 2), h);
+    return true;
   }
+  if (kind == kTargetsEth) {
+    // a 40-character line must be hex, a 42-character line hex from its third character (the two leading characters
+    // are not looked at); hexs2bin takes either letter case
+    const char* hex = r == 40 ? aux.c_str() : r == 42 ? aux.c_str() + 2 : nullptr;
+    if (!hex || !all_hex(hex)) return false;
+    hex20(hex, h);
+    return true;
+  }
+  if (r == 40 && all_hex(aux.c_str())) {   // -m rmd160: the hash160 itself
+    hex20(aux.c_str(), h);
+    return true;
+  }
+  uint8_t raw[25];
+  if (r == 0 || r >= 40 || !all_b58(aux.c_str()) || !b58decode25(aux.c_str(), raw)) return false;
+  memcpy(h.data(), raw + 1, 20);
+  return true;
+}
+
+// forceReadFileAddress (keyhunt.cpp:6300-6358), forceReadFileAddressEth (6374-6450), forceReadFileXPoint (6454-6552):
+// the lines long enough to count size the bloom and give the number of lines read from the top of the file, valid
+// or not (the reference's i < numberItems with numberItems-- per invalid line, or its i over lines: the same rule).
+bool AddrTargets::load_text(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err,
+                            TargetKind kind) {
+  T = AddrTargets();
+  T.eth = kind == kTargetsEth;
+  T.xpoint = kind == kTargetsXpoint;
+  const std::vector<std::string> lines = fgets_lines(text, kind == kTargetsXpoint ? 1000 : 100);
+  const size_t min_len = kind == kTargetsBtc ? 21 : 40;
+  for (const std::string& l : lines)
+    if (trimmed(l).size() >= min_len) ++T.counted;
   // initBloomFilter (keyhunt.cpp:6559-6576)
   const uint64_t entries = T.counted <= 10000 ? 10000 : (uint64_t)(bloom_multiplier > 0 ? bloom_multiplier : 1) * T.counted;
   if (T.bloom.init2(entries, 0.000001L) != 0) {
     if (err) *err = "bloom_init failed";
     return false;
   }
-  uint64_t items = T.counted, i = 0;
-  size_t li = 0;
-  while (i < items && li < lines.size()) {
-    snprintf(aux, sizeof aux, "%s", lines[li++].c_str());
-    trim(aux);
-    const size_t r = strlen(aux);
-    bool valid = false;
-    if (r > 0 && r <= 40) {
-      if (r < 40 && all_b58(aux)) {
-        uint8_t raw[25];
-        if (b58decode25(aux, raw)) {
-          H160 h;
-          memcpy(h.data(), raw + 1, 20);
-          T.bloom.add20(h.data());
-          T.table.push_back(h);
-          ++i;
-          valid = true;
-        }
-      }
-      if (r == 40 && all_hex(aux)) {
-        H160 h;
-        for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(aux[2 * k]) * 16 + hexv(aux[2 * k + 1]));
-        T.bloom.add20(h.data());
-        T.table.push_back(h);
-        ++i;
-        valid = true;
-      }
-    }
-    if (!valid) {
-      T.skipped.push_back(aux);
-      --items;
-    }
-  }
-  std::sort(T.table.begin(), T.table.end(),
-            [](const H160& a, const H160& b) { return memcmp(a.data(), b.data(), 20) < 0; });
-  return true;
-}
-
-// forceReadFileAddressEth (keyhunt.cpp:6374-6450): lines of 40 or more characters size the bloom; a 40-character
-// line must be hex, a 42-character line hex from its third character (the two leading characters are not looked
-// at); hexs2bin takes either letter case.
-bool AddrTargets::load_text_eth(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err) {
-  T = AddrTargets();
-  T.eth = true;
-  const std::vector<std::string> lines = fgets_lines(text);
-  char aux[128];
-  for (const std::string& l : lines) {
-    snprintf(aux, sizeof aux, "%s", l.c_str());
-    trim(aux);
-    if (strlen(aux) >= 40) ++T.counted;
-  }
-  const uint64_t entries = T.counted <= 10000 ? 10000 : (uint64_t)(bloom_multiplier > 0 ? bloom_multiplier : 1) * T.counted;
-  if (T.bloom.init2(entries, 0.000001L) != 0) {
-    if (err) *err = "bloom_init failed";
-    return false;
-  }
-  uint64_t items = T.counted, i = 0;
-  size_t li = 0;
-  while (i < items && li < lines.size()) {
-    snprintf(aux, sizeof aux, "%s", lines[li++].c_str());
-    trim(aux);
-    const size_t r = strlen(aux);
-    const char* hex = r == 40 ? aux : r == 42 ? aux + 2 : nullptr;
-    if (hex && all_hex(hex)) {
-      H160 h;
-      for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(hex[2 * k]) * 16 + hexv(hex[2 * k + 1]));
-      T.bloom.add20(h.data());
-      T.table.push_back(h);
-      ++i;
-    } else {
-      T.skipped.push_back(aux);
-      --items;
-    }
-  }
-  std::sort(T.table.begin(), T.table.end(),
-            [](const H160& a, const H160& b) { return memcmp(a.data(), b.data(), 20) < 0; });
-  return true;
-}
-
-// forceReadFileXPoint (keyhunt.cpp:6454-6552): fgets(aux, 1000); lines of 40 or more characters size the bloom and
-// give the number of lines read from the top of the file (the reference's i runs over lines, valid or not).
-bool AddrTargets::load_text_xpoint(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err) {
-  T = AddrTargets();
-  T.xpoint = true;
-  const std::vector<std::string> lines = fgets_lines(text, 1000);
-  for (const std::string& l : lines) {
-    std::string a = l;
-    a.resize(strlen(a.c_str()));
-    std::vector<char> aux(a.begin(), a.end());
-    aux.push_back(0);
-    trim(aux.data());
-    if (strlen(aux.data()) >= 40) ++T.counted;
-  }
-  const uint64_t entries = T.counted <= 10000 ? 10000 : (uint64_t)(bloom_multiplier > 0 ? bloom_multiplier : 1) * T.counted;
-  if (T.bloom.init2(entries, 0.000001L) != 0) {
-    if (err) *err = "bloom_init failed";
-    return false;
-  }
   for (size_t li = 0; li < T.counted && li < lines.size(); ++li) {
-    std::vector<char> aux(lines[li].c_str(), lines[li].c_str() + strlen(lines[li].c_str()) + 1);
-    trim(aux.data());
-    // stringtokenizer (util.c:67-84): trim "\t\n\r :", then the first strtok(" \t:") token
-    const char* tok = aux.data() + strspn(aux.data(), " \t:");
-    const size_t r = strcspn(tok, " \t:");
-    const std::string token(tok, r);
-    const char* hex = r == 64 || r == 130 ? token.c_str() : r == 66 ? token.c_str() + 2 : nullptr;
-    if (r == 130) hex += 2;          // 04 || x || y: x[0..19] for bloom and table (see address_host.hpp)
-    if (hex && all_hex(token.c_str())) {
-      H160 h;
-      for (int k = 0; k < 20; ++k) h[k] = (uint8_t)(hexv(hex[2 * k]) * 16 + hexv(hex[2 * k + 1]));
+    const std::string aux = trimmed(lines[li]);
+    H160 h;
+    if (line_h160(kind, aux, h)) {
       T.bloom.add20(h.data());
       T.table.push_back(h);
     } else {
-      T.skipped.push_back(aux.data());
+      T.skipped.push_back(aux);
     }
   }
   std::sort(T.table.begin(), T.table.end(),
@@ -324,7 +256,7 @@ bool AddrTargets::load_text_xpoint(const std::string& text, int bloom_multiplier
   return true;
 }
 
-bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err, int kind) {
+bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets& T, std::string* err, TargetKind kind) {
   FILE* f = fopen(path, "r");
   if (!f) {
     if (err) *err = std::string("Error opening the file ") + path;
@@ -335,9 +267,7 @@ bool AddrTargets::load_file(const char* path, int bloom_multiplier, AddrTargets&
   size_t n;
   while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
   fclose(f);
-  return kind == 2   ? load_text_xpoint(text, bloom_multiplier, T, err)
-         : kind == 1 ? load_text_eth(text, bloom_multiplier, T, err)
-                     : load_text(text, bloom_multiplier, T, err);
+  return load_text(text, bloom_multiplier, T, err, kind);
 }
 
 bool AddrTargets::searchbinary(const uint8_t data[20]) const {
@@ -484,81 +414,45 @@ struct AddrShared {
   int rc = 0;
 };
 
+struct ABatch : BatchRange {
+  std::vector<U256> bases;
+  std::vector<uint8_t> centres;
+  size_t jobs() const { return bases.size(); }
+  void slice(size_t j0, size_t j1, ABatch& o) const {
+    o.bases.assign(bases.begin() + j0, bases.begin() + j1);
+    o.centres.assign(centres.begin() + 64 * j0, centres.begin() + 64 * j1);
+  }
+};
 
-void device_loop(AddrShared& S, int device) {
-  khb_ctx* ctx = nullptr;
-  int rc = khb_open(device, S.cfg.lanes, &ctx);
-  auto fail = [&](int code, const char* what) {
+// One device's side of the launch pipeline (pipeline.hpp run_pipeline): chunk claiming, the khb_addr_submit /
+// khb_addr_collect calls and their buffer, the confirmation of the hits and the statistics.  A batch whose bloom
+// hits overflowed the ring is rescanned in two parts (by chunks, or one chunk by a gpl-aligned group range), queued
+// ahead of new chunks: every hit reaches confirm_hit, as every hit reaches searchbinary in the reference
+// (keyhunt.cpp:2716-2937).
+struct AddrOps {
+  AddrShared& S;
+  khb_ctx* ctx;
+  const int device;
+  const uint32_t groups;               // of a whole chunk
+  uint64_t per_batch = 1;              // chunks claimed per launch
+  std::vector<khb_addr_hit> hits{};
+  uint32_t acap = 0;                   // hits a launch keeps: the ring's capacity, at most hits.size()
+  khb_stats st{};                      // the launch collected last
+  // after a stop (the caller's stop) the prepared batch is dropped instead of queued, so the exit waits for at most
+  // the one launch still in flight
+  static constexpr bool drop_on_stop = true;
+
+  int fail(int code, const char* what) {
     std::lock_guard<std::mutex> lk(S.mu);
     if (!S.rc) {
       S.rc = code;
       S.err = std::string(what) + ": " + khb_strerror(code);
     }
-  };
-  if (rc) return fail(rc, "khb_open");
-  const uint32_t groups = (uint32_t)(S.cfg.n_seq / 1024);
-  const std::vector<uint8_t> gtab = S.G.table_be(), offs = S.G.offs_be();
-  const BloomGeom bg = S.T.bloom.geom();
-  if ((S.cfg.hit_cap && (rc = khb_set_candidate_capacity(ctx, S.cfg.hit_cap))) ||
-      (rc = khb_load_giant_table(ctx, gtab.data())) ||
-      (rc = khb_load_lane_offsets(ctx, offs.data(), (uint32_t)S.G.offs.size(), S.G.gpl)) ||
-      (rc = khb_load_addr_bloom(ctx, S.T.bloom.bf.data(), bg.bytes_per_sub, bg.bits, bg.hashes))) {
-    khb_close(ctx);
-    return fail(rc, "table upload");
+    return code;
   }
-  const uint64_t lanes_per_job = (groups + S.G.gpl - 1) / S.G.gpl;
-  const uint64_t lanes = khb_lanes(ctx);
-  // about eight work items per lane (the kernel's waves take items dynamically, so a deep launch
-  // keeps every SIMD full until its last items), and two launches queued (the context's two
-  // submission slots): the next launch fills the CUs the current one's tail leaves idle
-  uint64_t per_batch = (8 * lanes + lanes_per_job - 1) / lanes_per_job;
-  if (per_batch < 1) per_batch = 1;
-  if (per_batch > 4096) per_batch = 4096;
-  struct ABatch {
-    std::vector<U256> bases;
-    std::vector<uint8_t> centres;
-    uint32_t group_begin = 0, group_count = 0;   // group range of every chunk (0 = the whole chunk)
-    bool part = false;                           // a rescan part of a batch whose hits overflowed
-  };
-  ABatch ring[3];
-  int next = 0;
-  auto take = [&]() { const int i = next; next = (next + 1) % 3; return i; };
-  const U256 half = S.G.stride * 512u;
-  // A batch whose bloom hits overflowed the ring is rescanned in two parts (by chunks, or one chunk by
-  // a gpl-aligned group range), queued ahead of new chunks: every hit reaches confirm_hit, as every
-  // hit reaches searchbinary in the reference (keyhunt.cpp:2716-2937).
-  std::deque<ABatch> parts;
-  auto split = [&](const ABatch& b, ABatch& lo, ABatch& hi) {
-    const size_t n = b.bases.size();
-    const uint32_t g0 = b.group_begin, gc = b.group_count ? b.group_count : groups;
-    auto part = [&](ABatch& o, size_t j0, size_t j1, uint32_t pb, uint32_t pc) {
-      o.bases.assign(b.bases.begin() + j0, b.bases.begin() + j1);
-      o.centres.assign(b.centres.begin() + 64 * j0, b.centres.begin() + 64 * j1);
-      o.group_begin = pb;
-      o.group_count = pc;
-      o.part = true;
-    };
-    if (n > 1) {
-      part(lo, 0, n / 2, g0, gc);
-      part(hi, n / 2, n, g0, gc);
-      return true;
-    }
-    if (n == 0 || gc <= S.G.gpl) return false;
-    const uint32_t h = (gc / 2 + S.G.gpl - 1) / S.G.gpl * S.G.gpl;
-    part(lo, 0, 1, g0, h);
-    part(hi, 0, 1, g0 + h, gc - h);
-    return true;
-  };
-  auto prepare = [&](ABatch& b) {
+  bool stopped() { return S.cb.stop && S.cb.stop(); }
+  bool fresh(ABatch& b) {
     b.bases.clear();
-    if (S.cb.stop && S.cb.stop()) return false;
-    if (!parts.empty()) {
-      b = std::move(parts.front());
-      parts.pop_front();
-      return true;
-    }
-    b.group_begin = b.group_count = 0;
-    b.part = false;
     {
       std::lock_guard<std::mutex> lk(S.mu);
       if (S.rc) return false;
@@ -577,6 +471,7 @@ void device_loop(AddrShared& S, int device) {
     if (b.bases.empty()) return false;
     if (S.cb.on_chunk)
       for (const U256& c : b.bases) S.cb.on_chunk(c, device);
+    const U256 half = S.G.stride * 512u;
     b.centres.resize(64 * b.bases.size());
     for (size_t k = 0; k < b.bases.size(); ++k) {
       U256 c = b.bases[k] + half, r;   // startP = ComputePublicKey(key_mpz + 512*stride)
@@ -584,72 +479,28 @@ void device_loop(AddrShared& S, int device) {
       pt_to_be(b.centres.data() + 64 * k, mul_g(r));
     }
     return true;
-  };
-  auto submit = [&](ABatch& b) {
-    return khb_addr_submit(ctx, b.centres.data(), (uint32_t)b.bases.size(), b.group_begin,
-                           b.group_count ? b.group_count : groups,
-                           S.cfg.search | (S.cfg.endomorphism ? KHB_SEARCH_ENDOMORPHISM : 0));
-  };
-  // both submission slots up front; on KHB_ENOMEM (large targets or many devices' worth of scratch)
-  // one launch at a time instead of failing (advisor r2)
-  size_t depth = 2;
-  if ((rc = khb_reserve_slots(ctx, 2)) == KHB_ENOMEM) {
-    depth = 1;
-    rc = 0;
-    std::lock_guard<std::mutex> lk(S.mu);
-    if (S.cb.on_warning) S.cb.on_warning("[W] no device memory for a second submission slot: one batch in flight");
-  } else if (rc) {
-    khb_close(ctx);
-    return fail(rc, "khb_reserve_slots");
   }
-  std::vector<khb_addr_hit> hits(1u << 18);
-  std::deque<int> q;
-  while (q.size() < depth) {
-    const int i = take();
-    if (!prepare(ring[i])) break;
-    if ((rc = submit(ring[i]))) { fail(rc, "khb_addr_submit"); break; }
-    q.push_back(i);
+  int submit(const ABatch& b) {
+    const int rc = khb_addr_submit(ctx, b.centres.data(), (uint32_t)b.bases.size(), b.group_begin,
+                                   b.group_count ? b.group_count : groups,
+                                   S.cfg.search | (S.cfg.endomorphism ? KHB_SEARCH_ENDOMORPHISM : 0));
+    return rc ? fail(rc, "khb_addr_submit") : 0;
   }
-  const uint32_t acap = std::min<uint32_t>(khb_addr_hit_capacity(ctx), (uint32_t)(1u << 18));
-  int pre = -1;
-  while (!q.empty()) {
-    if (pre < 0 && !rc && prepare(ring[next])) pre = take();   // overlaps the GPU scan
-    const int i = q.front();
-    q.pop_front();
-    khb_stats st{};
-    const int crc = khb_addr_collect(ctx, hits.data(), (uint32_t)hits.size(), &st);
-    if (crc) { fail(crc, "khb_addr_collect"); rc = crc; continue; }   // keep draining the queue
-    // after a stop (every target found, or the caller's stop) the prepared batch is dropped instead of
-    // queued, so the exit waits for at most the one launch still in flight (advisor r2)
-    if (pre >= 0 && !rc && !(S.cb.stop && S.cb.stop())) {
-      if ((rc = submit(ring[pre]))) fail(rc, "khb_addr_submit");
-      else q.push_back(pre);
-    }
-    pre = -1;
-    if (rc) continue;
-    const ABatch& b = ring[i];
+  int collect() {
+    st = khb_stats{};
+    const int rc = khb_addr_collect(ctx, hits.data(), (uint32_t)hits.size(), &st);
+    return rc ? fail(rc, "khb_addr_collect") : 0;
+  }
+  int done(const ABatch& b, ABatch& lo, ABatch& hi) {
     if (st.n_cand > acap) {              // the ring kept only acap hits: rescan the batch in parts
-      ABatch lo, hi;
-      if (!split(b, lo, hi)) {
-        fail(-100, "bloom hit ring overflow on a single work item (target bloom too full)");
-        rc = -100;
-        continue;
-      }
-      parts.push_front(std::move(hi));
-      parts.push_front(std::move(lo));
-      {
-        std::lock_guard<std::mutex> lk(S.mu);
-        S.stats.launches++;
-        S.stats.rescans++;
-        S.stats.kernel_seconds += st.kernel_ms * 1e-3;
-        if (!b.part) S.stats.chunks += b.bases.size();
-      }
-      if (q.empty() && pre < 0 && prepare(ring[next])) {    // keep the device busy with the parts
-        const int k = take();
-        if ((rc = submit(ring[k]))) fail(rc, "khb_addr_submit");
-        else q.push_back(k);
-      }
-      continue;
+      if (!split_batch(b, groups, S.G.gpl, lo, hi))
+        return fail(-100, "bloom hit ring overflow on a single work item (target bloom too full)");
+      std::lock_guard<std::mutex> lk(S.mu);
+      S.stats.launches++;
+      S.stats.rescans++;
+      S.stats.kernel_seconds += st.kernel_ms * 1e-3;
+      if (!b.part) S.stats.chunks += b.bases.size();
+      return kRescan;
     }
     const uint32_t nh = st.n_cand;
     std::sort(hits.begin(), hits.begin() + nh, [](const khb_addr_hit& x, const khb_addr_hit& y) {
@@ -679,6 +530,38 @@ void device_loop(AddrShared& S, int device) {
     S.stats.found += found.size();
     if (S.cb.on_found)
       for (const AddrFound& f : found) S.cb.on_found(f);
+    return 0;
+  }
+};
+
+void device_loop(AddrShared& S, int device) {
+  AddrOps ops{S, nullptr, device, (uint32_t)(S.cfg.n_seq / 1024)};
+  khb_ctx*& ctx = ops.ctx;
+  int rc = khb_open(device, S.cfg.lanes, &ctx);
+  if (rc) { ops.fail(rc, "khb_open"); return; }
+  const std::vector<uint8_t> gtab = S.G.table_be(), offs = S.G.offs_be();
+  const BloomGeom bg = S.T.bloom.geom();
+  int depth = 2;
+  if ((S.cfg.hit_cap && (rc = khb_set_candidate_capacity(ctx, S.cfg.hit_cap))) ||
+      (rc = khb_load_giant_table(ctx, gtab.data())) ||
+      (rc = khb_load_lane_offsets(ctx, offs.data(), (uint32_t)S.G.offs.size(), S.G.gpl)) ||
+      (rc = khb_load_addr_bloom(ctx, S.T.bloom.bf.data(), bg.bytes_per_sub, bg.bits, bg.hashes))) {
+    ops.fail(rc, "table upload");
+  } else if ((rc = reserve_depth(depth, KHB_ENOMEM, [&](int n) { return khb_reserve_slots(ctx, n); },
+                                 [&](const char* m) {   // large targets or many devices' worth of scratch
+                                   std::lock_guard<std::mutex> lk(S.mu);
+                                   if (S.cb.on_warning) S.cb.on_warning(m);
+                                 }))) {
+    ops.fail(rc, "khb_reserve_slots");
+  } else {
+    // about eight work items per lane (the kernel's waves take items dynamically, so a deep launch keeps every SIMD
+    // full until its last items), and two launches queued (the context's two submission slots): the next launch
+    // fills the CUs the current one's tail leaves idle
+    const uint64_t lanes_per_job = (ops.groups + S.G.gpl - 1) / S.G.gpl;
+    ops.per_batch = std::min<uint64_t>(4096, std::max<uint64_t>(1, (8ull * khb_lanes(ctx) + lanes_per_job - 1) / lanes_per_job));
+    ops.hits.resize(1u << 18);
+    ops.acap = std::min<uint32_t>(khb_addr_hit_capacity(ctx), (uint32_t)ops.hits.size());
+    run_pipeline<ABatch>(ops, depth);
   }
   khb_close(ctx);
 }

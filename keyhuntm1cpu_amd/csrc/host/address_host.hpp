@@ -31,28 +31,34 @@ void hash160_x(uint8_t prefix, const Pt& p, uint8_t out[20]);
 void eth_address_xy(const uint8_t xy[64], uint8_t out[20]);
 void eth_address_pub(const Pt& p, uint8_t out[20]);
 
+// What a target file's lines are (the khh_addr_new* entry points of include/khhost.h choose one)
+enum TargetKind {
+  kTargetsBtc = 0,      // -m address / -m rmd160: base58 P2PKH addresses or 40-hex hash160 (forceReadFileAddress)
+  kTargetsEth = 1,      // -c eth: 40-hex lines, with or without a two-character prefix (forceReadFileAddressEth)
+  kTargetsXpoint = 2,   // -m xpoint: public keys or x coordinates (forceReadFileXPoint)
+};
+
 struct AddrTargets {
   std::vector<H160> table;             // sorted (memcmp), the reference's addressTable after _sort
   BloomFilter bloom;                   // initBloomFilter(counted lines)
-  uint64_t counted = 0;                // lines longer than 20 characters (sizes the bloom)
-  std::vector<std::string> skipped;    // "[I] Ommiting invalid line"
-  bool eth = false;                    // -c eth: the table holds ETH addresses (load_text_eth)
-  bool xpoint = false;                 // -m xpoint: the table holds the first 20 bytes of x (load_text_xpoint)
+  uint64_t counted = 0;                // lines long enough to count (sizes the bloom)
+  std::vector<std::string> skipped;    // "[I] Ommiting invalid line": the trimmed lines
+  bool eth = false;                    // -c eth: the table holds ETH addresses (kTargetsEth)
+  bool xpoint = false;                 // -m xpoint: the table holds the first 20 bytes of x (kTargetsXpoint)
 
-  // text: the target file's contents.  Returns false with *err on an unusable bloom.
-  static bool load_text(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
-  // -c eth: 40-hex lines, with or without a two-character prefix (forceReadFileAddressEth); counted = lines of
-  // 40 or more characters
-  static bool load_text_eth(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
-  // -m xpoint (forceReadFileXPoint, keyhunt.cpp:6454-6552): counted = lines of 40 or more characters, and that many
-  // lines are read from the top of the file.  The first token (separators: space, tab, ':') decides: 64 hex = x,
-  // 66 hex = a compressed key whose two prefix characters are dropped unchecked, 130 hex = an uncompressed key;
-  // anything else goes to `skipped` and not into the table (the reference keeps a zero entry for it).  Table and
-  // bloom hold the first 20 bytes of x.  Deviation: for a 130-hex line the reference adds 04 || x[0..18] to the bloom
-  // and stores x[1..20] in the table (6524-6528), so such a line can never be found there; here both take x[0..19].
-  static bool load_text_xpoint(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err);
-  // kind: 0 = load_text, 1 = load_text_eth, 2 = load_text_xpoint
-  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err, int kind = 0);
+  // text: the target file's contents.  Returns false with *err on an unusable bloom.  counted = lines of more than 20
+  // characters (BTC) or of 40 or more (ETH, xpoint), and that many lines are read from the top of the file.
+  // BTC: a valid base58 line of under 40 characters, or a 40-hex line.
+  // ETH: a 40-hex line, or a 42-character line whose last 40 are hex (its first two characters are not looked at).
+  // xpoint (keyhunt.cpp:6454-6552): the first token (separators: space, tab, ':') decides: 64 hex = x, 66 hex = a
+  // compressed key whose two prefix characters are dropped unchecked, 130 hex = an uncompressed key; anything else
+  // goes to `skipped` and not into the table (the reference keeps a zero entry for it).  Table and bloom hold the
+  // first 20 bytes of x.  Deviation: for a 130-hex line the reference adds 04 || x[0..18] to the bloom and stores
+  // x[1..20] in the table (6524-6528), so such a line can never be found there; here both take x[0..19].
+  static bool load_text(const std::string& text, int bloom_multiplier, AddrTargets& out, std::string* err,
+                        TargetKind kind = kTargetsBtc);
+  static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err,
+                        TargetKind kind = kTargetsBtc);
   bool searchbinary(const uint8_t h[20]) const;   // keyhunt.cpp:2311-2335, literal
 };
 
@@ -68,8 +74,8 @@ struct AddrGen {
 
 struct AddrConfig {
   int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300),
-                                       // KHB_SEARCH_ETH (-c eth; the targets must be load_text_eth's) or
-                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be load_text_xpoint's)
+                                       // KHB_SEARCH_ETH (-c eth; the targets must be kTargetsEth's) or
+                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be kTargetsXpoint's)
   bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and (BTC) negated points
   U256 start{1}, end{1};               // [start, end): n_range_start / n_range_end
   uint64_t n_seq = 1ull << 32;         // keys per claimed chunk (-n, N_SEQUENTIAL_MAX)

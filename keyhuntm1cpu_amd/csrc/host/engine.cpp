@@ -8,12 +8,12 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <deque>
 #include <mutex>
 #include <random>
 #include <thread>
 
 #include "../../../include/khbsgs.h"
+#include "pipeline.hpp"
 
 namespace khb {
 
@@ -112,41 +112,18 @@ struct Shared {
   }
 };
 
-struct Batch {
+struct Batch : BatchRange {
   std::vector<U256> bases;        // chunk bases, in claim order
   std::vector<uint32_t> job_chunk, job_target;
   std::vector<uint8_t> centres;   // 64 B per job
-  uint32_t group_begin = 0;       // groups [group_begin, group_begin + group_count) of every job;
-  uint32_t group_count = 0;       // 0 = the whole chunk
-  bool part = false;              // a rescan part of a batch whose candidate ring overflowed
-};
-
-// The two halves of a batch whose candidates overflowed the ring (the caller rescans):
-// by jobs, or a single job by its group range, cut at a multiple of gpl (khb_submit's alignment).
-// false: a single job of at most gpl groups (cannot be split further).
-bool split_batch(const Batch& b, uint32_t cycles, uint32_t gpl, Batch& lo, Batch& hi) {
-  const size_t nj = b.job_chunk.size();
-  const uint32_t g0 = b.group_begin, gc = b.group_count ? b.group_count : cycles;
-  auto part = [&](Batch& o, size_t j0, size_t j1, uint32_t pb, uint32_t pc) {
-    o.bases = b.bases;
-    o.job_chunk.assign(b.job_chunk.begin() + j0, b.job_chunk.begin() + j1);
-    o.job_target.assign(b.job_target.begin() + j0, b.job_target.begin() + j1);
-    o.centres.assign(b.centres.begin() + 64 * j0, b.centres.begin() + 64 * j1);
-    o.group_begin = pb;
-    o.group_count = pc;
-    o.part = true;
-  };
-  if (nj > 1) {
-    part(lo, 0, nj / 2, g0, gc);
-    part(hi, nj / 2, nj, g0, gc);
-    return true;
+  size_t jobs() const { return job_chunk.size(); }
+  void slice(size_t j0, size_t j1, Batch& o) const {   // job_chunk indexes the whole bases
+    o.bases = bases;
+    o.job_chunk.assign(job_chunk.begin() + j0, job_chunk.begin() + j1);
+    o.job_target.assign(job_target.begin() + j0, job_target.begin() + j1);
+    o.centres.assign(centres.begin() + 64 * j0, centres.begin() + 64 * j1);
   }
-  if (nj == 0 || gc <= gpl) return false;
-  const uint32_t half = (gc / 2 + gpl - 1) / gpl * gpl;     // gpl <= half < gc
-  part(lo, 0, 1, g0, half);
-  part(hi, 0, 1, g0 + half, gc - half);
-  return true;
-}
+};
 
 // Device-busy time of one context's launches: the length of the union of their [begin, end) intervals
 // (ms on the context's epoch).  Launches are collected in submission order and at most two overlap, so
@@ -338,109 +315,57 @@ uint32_t batch_chunks(const Tables& T, const SearchConfig& cfg, size_t ntargets,
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(jobs / std::max<size_t>(1, ntargets), 65536));
 }
 
-// One device: up to `queue_depth` batches queued on the GPU (khb_submit fills the context's next
-// slot, each on its own stream, so a queued batch takes over the CUs the running one's last waves
-// free); the next batch is claimed and centred while the GPU scans, and each collected batch is
-// confirmed after its successor has been submitted.  A batch whose candidates overflowed the ring
-// is rescanned in two parts (split_batch, recursively), queued ahead of new chunks.
-void device_thread(Shared& S, khb_ctx* ctx) {
-  auto fail = [&](int rc, const char* what) {
+// One device's side of the launch pipeline (pipeline.hpp run_pipeline: up to `queue_depth` batches queued on the
+// GPU, khb_submit filling the context's next slot, each on its own stream, so a queued batch takes over the CUs the
+// running one's last waves free): chunk claiming, the khb_submit / khb_collect calls and their buffers,
+// confirmation and the statistics.
+struct DeviceOps {
+  Shared& S;
+  khb_ctx* ctx;
+  const uint32_t cycles, want;
+  const int threads;
+  std::vector<khb_cand> cbuf = std::vector<khb_cand>(1u << 20);
+  std::vector<khb_degenerate> dbuf = std::vector<khb_degenerate>(4096);
+  uint32_t cap = 0;
+  BusyUnion busy{};
+  khb_stats st{};                      // the launch collected last
+  std::vector<khb_cand> cands{};
+  bool device_check_off = false;       // a failed khb_check moves this device's confirmations to the host
+  static constexpr bool drop_on_stop = false;
+
+  int fail(int rc, const char* what) {
     std::lock_guard<std::mutex> lk(S.mu);
     if (!S.error) {
       S.error = rc;
       S.err = std::string("[E] ") + what + ": " + khb_strerror(rc);
     }
     S.stop = true;
-  };
-  auto warn = [&](const std::string& m) {
-    std::lock_guard<std::mutex> lk(S.mu);
-    if (S.cb.on_warning) S.cb.on_warning(m);
-  };
-  const Tables& T = S.T;
-  const uint32_t cycles = (uint32_t)T.geo.cycles;
-  const uint32_t want = batch_chunks(T, S.cfg, S.targets.size(), khb_lanes(ctx));
-  const int threads = S.cfg.check_threads > 0 ? S.cfg.check_threads
-                                               : (int)std::max(2u, std::min(16u, std::thread::hardware_concurrency()));
-  int depth = std::max(1, std::min(S.cfg.queue_depth, 2));
-  if (depth > 1) {
-    // the second slot's scratch (~35 GB at the default lanes) up front; without it the device runs one
-    // batch at a time
-    const int rrc = khb_reserve_slots(ctx, depth);
-    if (rrc == KHB_ENOMEM) {
-      depth = 1;
-      warn("[W] no device memory for a second submission slot: one batch in flight");
-    } else if (rrc) {
-      fail(rrc, "khb_reserve_slots");
-      return;
-    }
+    return rc;
   }
-  std::vector<khb_cand> cbuf(1u << 20);
-  std::vector<khb_degenerate> dbuf(4096);
-  const uint32_t cap = std::min<uint32_t>(khb_candidate_capacity(ctx), (uint32_t)cbuf.size());
-  std::vector<Batch> ring(depth + 1);
-  std::deque<Batch> parts;    // rescan parts of overflowed batches, submitted before new chunks
-  BusyUnion busy;
-  int next = 0;               // ring slots are used and released in FIFO order
-  auto take = [&]() { const int i = next; next = (next + 1) % (int)ring.size(); return i; };
-  auto stopped = [&]() { std::lock_guard<std::mutex> lk(S.mu); return S.stop; };
-  auto prepare = [&](Batch& b) {
-    if (stopped()) return false;
-    if (!parts.empty()) {
-      b = std::move(parts.front());
-      parts.pop_front();
-      return true;
-    }
+  bool stopped() {
+    std::lock_guard<std::mutex> lk(S.mu);
+    return S.stop;
+  }
+  bool fresh(Batch& b) {
     if (!claim(S, want, b)) return false;
-    b.group_begin = b.group_count = 0;
-    b.part = false;
     make_jobs(S, b, threads);
     return !b.job_chunk.empty();
-  };
-  auto submit = [&](Batch& b) {
-    return khb_submit(ctx, b.centres.data(), (uint32_t)b.job_chunk.size(), b.group_begin,
-                      b.group_count ? b.group_count : cycles);
-  };
-  int rc = khb_reset_epoch(ctx);
-  if (rc) { fail(rc, "khb_reset_epoch"); return; }
-  std::deque<int> q;          // batches on the GPU, oldest first
-  auto fill = [&]() {         // queue up to `depth` batches (start, and after a rescan drained the queue)
-    while (!rc && (int)q.size() < depth) {
-      if (!prepare(ring[next])) break;
-      const int i = take();
-      if ((rc = submit(ring[i]))) { fail(rc, "khb_submit"); break; }
-      q.push_back(i);
-    }
-  };
-  fill();
-  int pre = -1;               // claimed and centred, not yet submitted
-  std::vector<khb_cand> cands;
-  bool device_check_off = false;       // a failed khb_check moves this device's confirmations to the host
-  while (!q.empty()) {
-    if (pre < 0 && !rc && prepare(ring[next])) pre = take();   // overlaps the GPU scan
-    const int i = q.front();
-    q.pop_front();
-    khb_stats st{};
-    const int crc = khb_collect(ctx, cbuf.data(), (uint32_t)cbuf.size(), dbuf.data(), (uint32_t)dbuf.size(), &st);
-    if (crc) { fail(crc, "khb_collect"); rc = crc; continue; }  // keep draining the queue
-    if (pre >= 0 && !rc) {
-      if ((rc = submit(ring[pre]))) fail(rc, "khb_submit");
-      else q.push_back(pre);
-    }
-    pre = -1;
-    if (rc) continue;
-    const Batch& b = ring[i];
+  }
+  int submit(const Batch& b) {
+    const int rc = khb_submit(ctx, b.centres.data(), (uint32_t)b.job_chunk.size(), b.group_begin,
+                              b.group_count ? b.group_count : cycles);
+    return rc ? fail(rc, "khb_submit") : 0;
+  }
+  int collect() {
+    st = khb_stats{};
+    const int rc = khb_collect(ctx, cbuf.data(), (uint32_t)cbuf.size(), dbuf.data(), (uint32_t)dbuf.size(), &st);
+    return rc ? fail(rc, "khb_collect") : 0;
+  }
+  int done(const Batch& b, Batch& lo, Batch& hi) {
     busy.add(st.launch_begin_ms, st.launch_end_ms);
     const bool overflow = st.n_cand > cap;
-    if (overflow) {
-      Batch lo, hi;
-      if (!split_batch(b, cycles, T.gpl, lo, hi)) {
-        fail(KHB_ENOMEM, "candidate ring overflow on a single work item");
-        rc = KHB_ENOMEM;
-        continue;
-      }
-      parts.push_front(std::move(hi));
-      parts.push_front(std::move(lo));
-    }
+    if (overflow && !split_batch(b, cycles, S.T.gpl, lo, hi))
+      return fail(KHB_ENOMEM, "candidate ring overflow on a single work item");
     {
       std::lock_guard<std::mutex> lk(S.mu);
       S.stats.launches += 1;
@@ -453,29 +378,43 @@ void device_thread(Shared& S, khb_ctx* ctx) {
       if (!b.part) S.stats.chunks += b.bases.size();
       if (overflow) {
         S.stats.rescans += 1;
-      } else {
-        S.stats.giant_steps += st.giant_steps;
-        S.stats.candidates += st.n_cand;
-        S.stats.degenerate += st.n_degenerate;
-        for (uint32_t d = 0; d < st.n_degenerate && d < dbuf.size(); ++d) {
-          if (!S.cb.on_warning) break;
-          const uint32_t job = dbuf[d].job;
-          S.cb.on_warning("[W] collapsed batch inverse (target on a window centre): chunk 0x" +
-                          b.bases[b.job_chunk[job]].hex() + " group " + std::to_string(dbuf[d].group & 0x7fffffffu));
-        }
-        if (S.cfg.record_candidates && S.cb.on_candidate)
-          for (uint32_t c = 0; c < st.n_cand; ++c)
-            S.cb.on_candidate(b.bases[b.job_chunk[cbuf[c].job]], (int)b.job_target[cbuf[c].job], cbuf[c].a);
+        return kRescan;
       }
+      S.stats.giant_steps += st.giant_steps;
+      S.stats.candidates += st.n_cand;
+      S.stats.degenerate += st.n_degenerate;
+      for (uint32_t d = 0; d < st.n_degenerate && d < dbuf.size(); ++d) {
+        if (!S.cb.on_warning) break;
+        const uint32_t job = dbuf[d].job;
+        S.cb.on_warning("[W] collapsed batch inverse (target on a window centre): chunk 0x" +
+                        b.bases[b.job_chunk[job]].hex() + " group " + std::to_string(dbuf[d].group & 0x7fffffffu));
+      }
+      if (S.cfg.record_candidates && S.cb.on_candidate)
+        for (uint32_t c = 0; c < st.n_cand; ++c)
+          S.cb.on_candidate(b.bases[b.job_chunk[cbuf[c].job]], (int)b.job_target[cbuf[c].job], cbuf[c].a);
     }
-    if (!overflow) {
-      cands.assign(cbuf.begin(), cbuf.begin() + st.n_cand);
-      confirm(S, ctx, b, cands, threads, device_check_off);    // overlaps the GPU scan of the queue
-    }
-    if (q.empty()) fill();     // rescan parts left after the last batch
+    cands.assign(cbuf.begin(), cbuf.begin() + st.n_cand);
+    confirm(S, ctx, b, cands, threads, device_check_off);
+    return 0;
   }
+};
+
+void device_thread(Shared& S, khb_ctx* ctx) {
+  const int threads = S.cfg.check_threads > 0 ? S.cfg.check_threads
+                                               : (int)std::max(2u, std::min(16u, std::thread::hardware_concurrency()));
+  DeviceOps ops{S, ctx, (uint32_t)S.T.geo.cycles, batch_chunks(S.T, S.cfg, S.targets.size(), khb_lanes(ctx)), threads};
+  // the second slot's scratch (~35 GB at the default lanes) up front
+  int depth = std::max(1, std::min(S.cfg.queue_depth, 2));
+  int rc = reserve_depth(depth, KHB_ENOMEM, [&](int n) { return khb_reserve_slots(ctx, n); }, [&](const char* m) {
+    std::lock_guard<std::mutex> lk(S.mu);
+    if (S.cb.on_warning) S.cb.on_warning(m);
+  });
+  if (rc) { ops.fail(rc, "khb_reserve_slots"); return; }
+  ops.cap = std::min<uint32_t>(khb_candidate_capacity(ctx), (uint32_t)ops.cbuf.size());
+  if ((rc = khb_reset_epoch(ctx))) { ops.fail(rc, "khb_reset_epoch"); return; }
+  run_pipeline<Batch>(ops, depth);
   std::lock_guard<std::mutex> lk(S.mu);
-  S.stats.busy_seconds += busy.ms() * 1e-3;
+  S.stats.busy_seconds += ops.busy.ms() * 1e-3;
 }
 
 }  // namespace

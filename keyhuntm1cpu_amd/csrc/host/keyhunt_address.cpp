@@ -101,7 +101,8 @@ int run_address_mode(const AddressCli& o) {
   AddrTargets T;
   std::string err;
   const bool xpoint = o.mode == 0;
-  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err, xpoint ? 2 : o.eth ? 1 : 0)) {
+  if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err,
+                              xpoint ? kTargetsXpoint : o.eth ? kTargetsEth : kTargetsBtc)) {
     fprintf(stderr, "[E] %s\n[E] Unenexpected error\n", err.c_str());
     return EXIT_FAILURE;
   }

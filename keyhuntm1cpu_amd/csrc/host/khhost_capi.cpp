@@ -392,7 +392,7 @@ int khh_parse_pubkey(const char* hex, uint8_t out_xy[64], int* compressed) {
   return 0;
 }
 
-static khh_addr* addr_new(int kind, const char* text, int bloom_multiplier, const uint8_t stride_be[32],
+static khh_addr* addr_new(TargetKind kind, const char* text, int bloom_multiplier, const uint8_t stride_be[32],
                           uint64_t n_seq, uint32_t gpl, int threads, char* err, size_t errlen) {
   if (!text || n_seq < 1024 || n_seq % 1024) {
     set_err(err, errlen, "n must be a positive multiple of 1024");
@@ -400,9 +400,7 @@ static khh_addr* addr_new(int kind, const char* text, int bloom_multiplier, cons
   }
   khh_addr* a = new khh_addr();
   std::string e;
-  if (!(kind == 2   ? AddrTargets::load_text_xpoint(text, bloom_multiplier, a->T, &e)
-        : kind == 1 ? AddrTargets::load_text_eth(text, bloom_multiplier, a->T, &e)
-                    : AddrTargets::load_text(text, bloom_multiplier, a->T, &e))) {
+  if (!AddrTargets::load_text(text, bloom_multiplier, a->T, &e, kind)) {
     set_err(err, errlen, e);
     delete a;
     return nullptr;
@@ -421,17 +419,17 @@ static khh_addr* addr_new(int kind, const char* text, int bloom_multiplier, cons
 
 khh_addr* khh_addr_new(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                        uint32_t gpl, int threads, char* err, size_t errlen) {
-  return addr_new(0, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+  return addr_new(kTargetsBtc, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
 }
 
 khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                            uint32_t gpl, int threads, char* err, size_t errlen) {
-  return addr_new(1, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+  return addr_new(kTargetsEth, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
 }
 
 khh_addr* khh_addr_new_xpoint(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                               uint32_t gpl, int threads, char* err, size_t errlen) {
-  return addr_new(2, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+  return addr_new(kTargetsXpoint, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
 }
 
 uint64_t khh_addr_counted(const khh_addr* a) { return a ? a->T.counted : 0; }

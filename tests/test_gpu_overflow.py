@@ -1,7 +1,7 @@
 """GPU: the candidate-ring overflow contract of SURVEY.md §8b.
 
 Every level-1 hit must reach bsgs_secondcheck (keyhunt.cpp:3944-3948 -> 4271-4368).  A launch keeps at
-most khb_candidate_capacity() candidates; when it counted more, the engine (engine.cpp device_thread)
+most khb_candidate_capacity() candidates; when it counted more, the engine (host/pipeline.hpp run_pipeline)
 splits the batch -- by jobs, then one job's groups -- and rescans the parts ahead of new chunks.  The
 candidates it then confirms must be exactly the oracle's level-1 candidates, and the device-counted
 giant steps must equal the submitted work once.

@@ -28,6 +28,18 @@ def _build_and_run(src: str, tmp_path) -> str:
     return r.stdout
 
 
+def test_launch_pipeline_on_host(tmp_path):
+    """host/pipeline.hpp (the launch pipeline of -m bsgs and -m address) with a scripted fake device: FIFO order,
+    queue depth, rescan parts ahead of new chunks and lo before hi, gpl-aligned cuts, draining after a submit or
+    collect error, and the stop switch.  Needs neither the oracle objects nor a GPU."""
+    exe = str(tmp_path / "test_pipeline_host")
+    subprocess.run(["g++", "-O2", "-std=c++17", os.path.join(HERE, "native", "test_pipeline_host.cpp"), "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "ok", r.stdout
+
+
 def test_device_math_headers_on_host(tmp_path):
     out = _build_and_run("test_device_math_host.cpp", tmp_path)
     assert "FAIL" not in out
