@@ -106,6 +106,9 @@ void ora_bsgs_scan(const ora_bsgs* c, const ora_point* startP, uint32_t j0, uint
                    uint8_t* xdump, uint64_t* cand, uint32_t cap, uint32_t* ncand, ora_point* next);
 /* keyhunt.cpp:4271-4304 (+4306-4368, 3748-3773, 6680-6689). 1 = found, key in *key. */
 int ora_bsgs_secondcheck(const ora_bsgs* c, const ora_u256* base, uint32_t a, const ora_point* target, ora_u256* key);
+/* bsgs_searchbinary (keyhunt.cpp:3748-3773) over any table of n entries: the key is bytes 16..21 of the 32-byte
+ * data.  1 = found, the landed entry's index in *rv. */
+int ora_bsgs_searchbinary(const ora_xvalue* buf, const uint8_t* data, int64_t n, uint64_t* rv);
 /* Sequential -t 1 search (keyhunt.cpp:3819-4006): chunks from start until end (or max_chunks),
  * targets in file order.  found[k] set to 1 and keys[k] filled for each found target.  Returns
  * the number of chunks processed. */

@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
                                     C.c_uint32, P(C.c_uint32), P(Point)]
         L.ora_bsgs_secondcheck.restype = C.c_int
         L.ora_bsgs_secondcheck.argtypes = [C.c_void_p, P(U256), C.c_uint32, P(Point), P(U256)]
+        L.ora_bsgs_searchbinary.restype = C.c_int
+        L.ora_bsgs_searchbinary.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, P(C.c_uint64)]
         L.ora_bsgs_search.restype = C.c_uint64
         L.ora_bsgs_search.argtypes = [C.c_void_p, P(Point), C.c_int, P(U256), P(U256), C.c_uint64, P(C.c_int),
                                       P(U256)]
@@ -176,6 +178,14 @@ def parse_pubkey(s: str) -> tuple[Point, bool] | None:
     if not lib().ora_parse_pubkey_hex(s.encode(), C.byref(p), C.byref(comp)):
         return None
     return p, bool(comp.value)
+
+
+def searchbinary(table: bytes, xb: bytes) -> int | None:
+    """bsgs_searchbinary over a table of 16-byte bsgs_xvalue entries for the 32-byte x: the landed index or None."""
+    rv = C.c_uint64(0)
+    if lib().ora_bsgs_searchbinary(table, xb, len(table) // 16, C.byref(rv)):
+        return int(rv.value)
+    return None
 
 
 def add_direct(a: Point, b: Point) -> Point:

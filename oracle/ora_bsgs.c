@@ -454,6 +454,10 @@ static int searchbinary(const ora_xvalue* buf, const uint8_t* data, int64_t n, u
   return r;
 }
 
+int ora_bsgs_searchbinary(const ora_xvalue* buf, const uint8_t* data, int64_t n, uint64_t* rv) {
+  return searchbinary(buf, data, n, rv);
+}
+
 /* calcualteindex (keyhunt.cpp:6680-6689): (2i+1)*M3 */
 static void calc_index(const ora_bsgs* c, int i, ora_u256* key) {
   if (i == 0) { *key = c->M3; return; }

@@ -1,6 +1,6 @@
 """Directed inputs for the rare-carry, canonicalisation and degenerate paths (test infrastructure).
 
-Three things live here, all on Python integers:
+Four things live here, all on Python integers:
 
   * secp256k1 affine arithmetic and finders of curve points whose x (or y) falls in a class that the
     lazy field arithmetic of csrc/device/fe_asm.hpp treats specially;
@@ -10,7 +10,9 @@ Three things live here, all on Python integers:
     and certifies that each one arithmetically requires the branch it is aimed at;
   * planting: start points such that a chosen step of a chosen group of the walk lands on a chosen point,
     the reference's rule for a group's centre, a reference of one -m address group from a centre (degenerate
-    groups included) and of one launch of a job as the library splits it over lanes.
+    groups included) and of one launch of a job as the library splits it over lanes;
+  * second_check_ref: bsgs_secondcheck / bsgs_thirdcheck with a report of what each of the 32 slots of every
+    batch did (tests/check_cases.py holds the directed cases that use it).
 """
 from __future__ import annotations
 
@@ -27,8 +29,9 @@ HALF = 512
 
 
 def inv(a: int) -> int:
-    """a^(p-2): the inverse, and 0 for 0 as the reference's ModInv."""
-    return pow(a, P - 2, P)
+    """The inverse mod p, and 0 for 0 as the reference's ModInv (a^(p-2))."""
+    a %= P
+    return pow(a, -1, P) if a else 0
 
 
 def on_curve(pt) -> bool:
@@ -509,3 +512,85 @@ def addr_lanes_ref(start, gn: list, offs: list, gpl: int, ngroups: int, cache: d
                 records.add(g)
             c = ref[1]
     return b"".join(xy), records
+
+
+# ------------------------------------------------------------------- the second / third check, per slot
+
+def bp_search(bp: bytes, xb: bytes):
+    """bsgs_searchbinary (keyhunt.cpp:3748-3773) transcribed: bp holds 16-byte entries (value[6], pad[2], index
+    u64 LE), the key is bytes 16..22 of xb.  The index of the entry the loop lands on, or None."""
+    n = len(bp) // 16
+    lo, hi, half, current = 0, n, n, 0
+    while half >= 1:
+        half = (hi - lo) // 2
+        e = 16 * (current + half)
+        v, k = bp[e:e + 6], xb[16:22]
+        if k == v:
+            return int.from_bytes(bp[e + 8:e + 16], "little")
+        if k < v:
+            hi = hi - half
+        else:
+            lo = lo + half
+        current = lo
+    return None
+
+
+def second_check_ref(tabs: dict, base: int, a: int, target) -> dict:
+    """bsgs_secondcheck / bsgs_thirdcheck (keyhunt.cpp:4271-4368, oracle/ora_bsgs.c) on Python integers, reporting
+    what every slot did.  tabs: the four constants m_double, m2_double, m3_value, m3_double (any width below 2^256,
+    sums modulo 2^256 as the device's U8), amp2 / amp3 / bptable as bytes, and "bs", the oracle geometry whose
+    (possibly altered) level-2 and level-3 sub-blooms answer membership.  k*G is the oracle's, 0 giving (0, 0);
+    AddDirect is add_direct_ref with inverse(0) = 0.  target: (x, y).
+    Returns key (or None), l2_hits, l3_hits, bp_hits, xs2 (the 32 second-check x), xs3 {i2: the 32 third-check x of
+    every third check entered} and zero, the (level, slot) of every batch element with dx == 0."""
+    import ctypes as C
+    from oracle import ora
+    bs, L, W = tabs["bs"], ora.lib(), 2**256
+    amp2, amp3, bp = table_points(tabs["amp2"]), table_points(tabs["amp3"]), tabs["bptable"]
+    res = {"key": None, "l2_hits": 0, "l3_hits": 0, "bp_hits": 0, "xs2": None, "xs3": {}, "zero": []}
+
+    def member(level, x):
+        xb = x.to_bytes(32, "big")
+        return bool(L.ora_bloom_check(C.byref(bs.bloom(level, xb[0])), xb, 32))
+
+    def minus_base(k):                     # target - k*G by AddDirect(target, Negation(k*G))
+        bx, by = ora.pubkey(k).xy()
+        return add_direct_ref(target, (bx, (P - by) % P))[0]
+
+    def batch(q, tab, level):
+        xs = []
+        for i in range(32):
+            pt, collapsed = add_direct_ref(q, tab[i])
+            xs.append(pt[0])
+            if collapsed:
+                res["zero"].append((level, i))
+        return xs
+
+    def third(base1, i2):
+        base2 = (base1 + i2 * tabs["m2_double"]) % W
+        q = minus_base(base2)
+        xs = res["xs3"][i2] = batch(q, amp3, 3)
+        for i in range(32):
+            ci = (i * tabs["m3_double"] + tabs["m3_value"]) % W
+            if member(3, xs[i]):
+                res["l3_hits"] += 1
+                j = bp_search(bp, xs[i].to_bytes(32, "big"))
+                if j is not None:
+                    res["bp_hits"] += 1
+                    for key in ((ci + j + 1) % W, (ci - j - 1) % W):
+                        key = (key + base2) % W
+                        if ora.pubkey(key).xy()[0] == target[0]:
+                            return key
+            elif q[0] == amp3[i][0]:
+                return (ci + base2) % W
+        return None
+
+    base1 = (base + a * tabs["m_double"]) % W
+    xs2 = res["xs2"] = batch(minus_base(base1), amp2, 2)
+    for i2 in range(32):
+        if member(2, xs2[i2]):
+            res["l2_hits"] += 1
+            res["key"] = third(base1, i2)
+            if res["key"] is not None:
+                break
+    return res

@@ -306,3 +306,158 @@ def test_oracle_batch_helpers(ora):
     with ora.AddrTable("\n".join(x.hex() for x in h[::2]) + "\n") as O:
         got = O.bloom_check_many(b"".join(h))
         assert list(got) == [1 if O.bloom_check(x) else 0 for x in h] and all(got[::2]) and not all(got)
+
+
+# ------------------------------------------------------- adv.second_check_ref, the per-slot model of the check
+
+@pytest.fixture(scope="module")
+def check_tabs(ora):
+    from tests import check_cases as cc
+    bs, tabs = cc.oracle_tables(ora)
+    yield cc, bs, tabs
+    bs.close()
+
+
+def _pin(cc, bs, tabs, cases):
+    """The model's key equals the oracle's bsgs_secondcheck on every case; the models are returned."""
+    out = []
+    for c in cases:
+        r = cc.model(bs, tabs, c)
+        assert r["key"] == bs.secondcheck(c.start, c.a, c.target), c.name
+        out.append(r)
+    return out
+
+
+def test_check_model_on_random_families(ora, check_tabs):
+    cc, bs, tabs = check_tabs
+    cases = cc.r_cases(ora, bs)
+    res = _pin(cc, bs, tabs, cases)
+    found = [r for r in res if r["key"] is not None]
+    assert len(found) >= 48 and sum(r["bp_hits"] for r in res) >= 32
+    special = [r for c, r in zip(cases, res) if "special" in c.name]
+    assert all(len(r["zero"]) == 1 and r["zero"][0][0] == 3 for r in special)       # Q' == -AMP3[i], that slot alone
+    # the same families with every level-2 / level-3 bit set
+    with cc.saved_blooms(bs, fill=0xFF):
+        res = _pin(cc, bs, tabs, cases[:6] + cases[48:51] + cases[-3:])
+        assert all(r["l2_hits"] == 32 and r["l3_hits"] == 1024 for r in res[-3:])
+    assert bs.bloom_concat(2) == tabs["l2"] and bs.bloom_concat(3) == tabs["l3"]
+
+
+def test_check_model_on_directed_cases(ora, check_tabs):
+    """Classes Z, K and C with the geometry's constants: the model's key is the oracle's, every Z case reaches the
+    dx == 0 element it is aimed at, and the other 31 x of that batch are plain point addition."""
+    cc, bs, tabs = check_tabs
+    amp = {2: adv.table_points(tabs["amp2"]), 3: adv.table_points(tabs["amp3"])}
+    res = _pin(cc, bs, tabs, cc.k_cases(ora, bs) + cc.c_cases(ora, bs))
+    assert [r["key"] is not None for r in res] == [False] * 5 + [True] * 18
+    assert _pin(cc, bs, tabs, [cc.wrap_case(ora, bs)])[0]["key"] is None     # the oracle's sums wrap at 2^256 too
+    assert all(r["bp_hits"] >= 1 for r in res[5:])
+    z2, z3 = cc.z2_cases(ora, bs), cc.z3_cases(ora, bs)
+    assert all(r["l2_hits"] == 0 for r in _pin(cc, bs, tabs, z3))      # unpinned: slot 0 does not enter
+    with cc.saved_blooms(bs):
+        cc.pin_z3_entry(ora, bs, tabs, z3)
+        cc.pin_batches(ora, bs, tabs, z2 + z3, skip_zero=True)
+        res = _pin(cc, bs, tabs, z2 + z3)
+    for c, r in zip(z2 + z3, res):
+        level, slot = cc.z_slot(c)
+        assert r["zero"] == [(level, slot)], c.name
+        xs = r["xs2"] if level == 2 else r["xs3"][0]
+        base2 = c.start + c.a * 2 * bs.m
+        q = adv.add(c.target.xy(), adv.neg(ora.pubkey(base2).xy()))
+        for i in range(32):
+            if i != slot:
+                assert xs[i] == adv.add(q, amp[level][i])[0], (c.name, i)
+        assert xs[slot] == (-2 * q[0]) % P                            # inverse 0: s = 0, x = -q.x - amp.x
+        if level == 2:
+            assert (r["key"], r["l2_hits"], r["l3_hits"]) == (None, 31, 31 * 32), c.name
+        else:                      # the reference returns base2 + (2i+1) m3 here, the key being base2 - (2i+1) m3
+            assert r["key"] == base2 + (2 * slot + 1) * bs.m3 and (r["l2_hits"], r["l3_hits"]) == (1, slot), c.name
+            assert ora.pubkey(r["key"]).xy()[0] != c.target.xy()[0]
+
+
+def test_check_model_equal_bptable_keys(ora, check_tabs):
+    """Runs of three equal 6-byte keys: the oracle's bsgs_searchbinary lands on the run's member that its probe
+    order 128, 64 / 192, ... reaches first, the one with the most trailing zero bits.  Observed split: the key at
+    an even centre p is found (p is that member), at an odd p it is lost (p - 1 or p + 1 is) - 18 found, 18 lost.
+    The model's transcription of the loop agrees case by case."""
+    cc, bs, tabs = check_tabs
+    cases = cc.d_cases(ora, bs)
+    assert all(r["key"] is not None for r in _pin(cc, bs, tabs, cases))
+    with cc.equal_key_runs(ora, bs):
+        t = cc.current_tabs(bs, tabs)
+        raw = t["bptable"]
+        assert [raw[16 * i:16 * i + 6] for i in range(256)] == sorted(raw[16 * i:16 * i + 6] for i in range(256))
+        assert raw != tabs["bptable"] and [raw[16 * i + 8:16 * i + 16] for i in range(256)] == \
+            [tabs["bptable"][16 * i + 8:16 * i + 16] for i in range(256)]
+        res = _pin(cc, bs, t, cases)
+    assert cc.bptable_raw(bs) == tabs["bptable"]
+    for c, r in zip(cases, res):
+        p = int(c.name[3:-1])
+        assert (r["key"] is not None) == (p % 2 == 0) and r["bp_hits"] == 1, c.name
+
+
+def test_check_model_table_of_200(ora, check_tabs):
+    """The bPtable cut to 200 entries (class T; the oracle's table size is fixed, so no oracle here): with distinct
+    keys the model finds every planted key, as any correct search must; with the runs it finds some and loses
+    others, and never reports a key whose point is not the target."""
+    cc, bs, tabs = check_tabs
+    cases = cc.t_cases(ora, bs)
+    cut = dict(tabs, bptable=tabs["bptable"][:16 * cc.T_ENTRIES], m3=cc.T_ENTRIES)
+    assert all(cc.model(bs, cut, c)["key"] is not None for c in cases)
+    with cc.equal_key_runs(ora, bs):
+        res = [cc.model(bs, cc.t_tabs(bs, tabs), c) for c in cases]
+    found = [r["key"] for r in res if r["key"] is not None]
+    assert 0 < len(found) < len(cases)
+    assert all(ora.pubkey(r["key"]).xy()[0] == c.target.xy()[0] for c, r in zip(cases, res) if r["key"] is not None)
+    print("class T:", len(found), "of", len(cases), "found")
+
+
+def test_check_model_pins_every_slot(ora, check_tabs):
+    """Level-2 and level-3 blooms that hold exactly the model's 32 + 32 x 32 x of four candidates: those give 32
+    and 1024 hits, four unrelated candidates none; the oracle finds nothing for any of them."""
+    cc, bs, tabs = check_tabs
+    pinned, other = cc.nothing_cases(ora, 4, 0x70696e), cc.nothing_cases(ora, 4, 0x6f7468)
+    with cc.saved_blooms(bs, fill=0):
+        cc.pin_batches(ora, bs, tabs, pinned)
+        res = _pin(cc, bs, tabs, pinned + other)
+    assert [(r["l2_hits"], r["l3_hits"]) for r in res] == [(32, 1024)] * 4 + [(0, 0)] * 4
+    assert bs.bloom_concat(2) == tabs["l2"] and bs.bloom_concat(3) == tabs["l3"]
+
+
+def test_bp_search_equals_the_oracle_at_every_table_size(ora):
+    """adv.bp_search against the oracle's bsgs_searchbinary on sorted tables of 1 to 300 entries with runs of equal
+    keys: every key of the table, its neighbours, and keys below and above all.  The landed index, not just found."""
+    rng = random.Random(0x6270)
+    landed_elsewhere = 0
+    for n in range(1, 301):
+        keys = sorted(rng.randrange(1, 2**48 - 1) for _ in range(n))
+        for _ in range(n // 6):                                       # runs of two to four equal keys
+            p = rng.randrange(n)
+            for q in range(p, min(n, p + rng.randrange(2, 5))):
+                keys[q] = keys[p]
+        keys.sort()
+        tab = b"".join(k.to_bytes(6, "big") + b"\0\0" + (n - 1 - i).to_bytes(8, "little") for i, k in enumerate(keys))
+        probes = set(keys) | {k + 1 for k in keys} | {k - 1 for k in keys} | {0, 2**48 - 1}
+        for k in probes:
+            xb = bytes(16) + k.to_bytes(6, "big") + bytes(10)
+            got = adv.bp_search(tab, xb)
+            assert got == ora.searchbinary(tab, xb), (n, k)
+            assert (got is not None) == (k in keys), (n, k)
+        landed_elsewhere += len(set(keys)) < n
+    assert landed_elsewhere > 200
+
+
+def test_bp_search_is_the_reference_loop():
+    """adv.bp_search on small tables by hand: every entry of a table of distinct keys is found (entry 0 by the
+    last probe, the one with half == 0), equal keys give the probe order's first member."""
+    def tab(keys):
+        return b"".join(k.to_bytes(6, "big") + b"\0\0" + i.to_bytes(8, "little") for i, k in enumerate(keys))
+
+    def xb(k):
+        return bytes(16) + k.to_bytes(6, "big") + bytes(10)
+    assert adv.bp_search(tab([5]), xb(5)) == 0 and adv.bp_search(tab([5]), xb(6)) is None
+    keys = [10, 20, 30, 40, 50, 60, 70, 80]
+    assert [adv.bp_search(tab(keys), xb(k)) for k in keys] == [0, 1, 2, 3, 4, 5, 6, 7]
+    assert adv.bp_search(tab(keys), xb(35)) is None
+    assert adv.bp_search(tab([10, 20, 20, 20, 50, 60, 70, 80]), xb(20)) == 2      # probes 4, 2
+    assert adv.bp_search(tab([10, 20, 30, 40, 40, 40, 70, 80]), xb(40)) == 4      # probes 4

@@ -13,59 +13,20 @@ import pytest
 
 from keyhuntm1cpu_amd import khhost
 from keyhuntm1cpu_amd.khbsgs import Engine
+from tests import check_cases
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-N_GEOM = "0x1000000000"        # N = 2^36: m = 2^18, m2 = 2^13, m3 = 2^8
-
-
-def _splitmix(seed):
-    s = seed
-    while True:
-        s = (s + 0x9E3779B97F4A7C15) & (2**64 - 1)
-        z = s
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2**64 - 1)
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2**64 - 1)
-        yield z ^ (z >> 31)
 
 
 @pytest.fixture(scope="module")
 def ora_tables(ora):
-    bs = ora.Bsgs(N_GEOM, 1)
-    # GTable: entry 256*i + b - 1 = b * 2^(8i) * G (b < 256); entry 256*i + 255 = 2^(8(i+1)) * G
-    parts = []
-    for i in range(32):
-        for b in range(1, 257):
-            parts.append(ora.pubkey(b << (8 * i)).be64())
-    gt = b"".join(parts)
-    bp = b"".join(v + b"\0\0" + idx.to_bytes(8, "little") for v, idx in bs.bptable())
-    tabs = {"gtable": gt, "amp2": bs.amp_table(2), "amp3": bs.amp_table(3), "l2": bs.bloom_concat(2),
-            "l3": bs.bloom_concat(3), "bptable": bp, "m3": bs.m3, "m_double": 2 * bs.m, "m2_double": 2 * bs.m2,
-            "m3_value": bs.m3, "m3_double": 2 * bs.m3}
+    bs, tabs = check_cases.oracle_tables(ora)
     yield bs, tabs
     bs.close()
 
 
-def _cases(ora, bs, seed):
-    """(base, a, target point, kind): planted keys across a candidate's window, the third check's
-    AddDirect(P, -P) case, random candidates."""
-    r = _splitmix(seed)
-    m, m2, m3 = bs.m, bs.m2, bs.m3
-    out = []
-    for _ in range(48):
-        base = next(r) | ((next(r) & 0xFFFF) << 64)
-        a = next(r) % 4096
-        key = base + a * 2 * m + next(r) % (2 * m + 64)
-        out.append((base, a, ora.pubkey(key), "planted"))
-    for _ in range(16):
-        base, a = next(r), next(r) % 4096
-        i2, i = next(r) % 32, next(r) % 32
-        key = base + a * 2 * m + i2 * 2 * m2 + i * 2 * m3 + m3
-        out.append((base, a, ora.pubkey(key), "special"))
-    for _ in range(32):
-        base = next(r) | (next(r) << 64) | ((next(r) >> 8) << 128)
-        out.append((base, next(r) & 0xFFFFFFFF, ora.pubkey(next(r) | (next(r) << 64) | (next(r) << 128)), "random"))
-    return out
+_cases = check_cases.random_cases
 
 
 def _run(ora, bs, tabs, cases):

@@ -12,16 +12,22 @@ REPO = os.path.dirname(HERE)
 ORACLE = os.path.join(REPO, "oracle")
 
 
-def _build_and_run(src: str, tmp_path) -> str:
+SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+
+
+def _build_and_run(src: str, tmp_path, sanitize: bool = False) -> str:
+    """Compile the stand-alone program tests/native/<src> with the oracle's objects and run it; sanitize: the
+    whole program (oracle objects included) under the host AddressSanitizer and UBSan."""
     subprocess.run(["make", "-s", "-C", ORACLE], check=True)
+    opt = SANITIZE if sanitize else ["-O2"]
     exe = str(tmp_path / os.path.splitext(os.path.basename(src))[0])
     srcs = [os.path.join(ORACLE, f) for f in ("ora_field.c", "ora_secp.c", "ora_hash.c", "ora_bsgs.c", "ora_addr.c")]
     objs = []
     for s in srcs:
         o = str(tmp_path / (os.path.basename(s) + ".o"))
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-c", s, "-o", o], check=True)
+        subprocess.run(["gcc", *opt, "-std=gnu11", "-c", s, "-o", o], check=True)
         objs.append(o)
-    subprocess.run(["g++", "-O2", "-std=c++17", os.path.join(HERE, "native", src), *objs, "-o", exe, "-lm",
+    subprocess.run(["g++", *opt, "-std=c++17", os.path.join(HERE, "native", src), *objs, "-o", exe, "-lm",
                     "-lpthread"], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -52,6 +58,15 @@ def test_hash160_header_on_host(tmp_path):
 
 def test_confirm_header_on_host(tmp_path):
     """device/confirm.hpp (khb_check's second/third check) vs the oracle's bsgs_secondcheck: planted keys,
-    the AddDirect(P, -P) special case, random candidates, and every level-2/3 bloom bit set."""
+    the AddDirect(P, -P) special case, random candidates, every level-2/3 bloom bit set, and the directed classes
+    of tests/check_cases.py (Z, K, C, D, blooms pinning every x, the U8 helpers, search_bp at 1 to 300 entries)."""
     out = _build_and_run("test_confirm_host.cpp", tmp_path)
+    assert out.strip().endswith("ok"), out
+    assert "oracle finds 18 at even centres, 0 at odd ones" in out, out
+
+
+def test_confirm_header_on_host_sanitized(tmp_path):
+    """The same stand-alone program under the host AddressSanitizer and UBSan: the 32-element batches, the bPtable
+    probes at both ends of the table and the byte windows of ck_mul_g stay inside their arrays."""
+    out = _build_and_run("test_confirm_host.cpp", tmp_path, sanitize=True)
     assert out.strip().endswith("ok"), out
