@@ -16,7 +16,7 @@ KHB_GROUP = 1024
 
 
 class KhbError(RuntimeError):
-    pass
+    code = 0                            # the KHB_E* value when a library call failed (_check)
 
 
 class Cand(C.Structure):
@@ -121,6 +121,11 @@ def lib(path: str | None = None) -> C.CDLL:
             L.khb_resident_read.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p]
             L.khb_resident_popcount.argtypes = [C.c_void_p, C.c_int, P(C.c_uint64)]
             L.khb_gate_probe.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
+        if hasattr(L, "khb_build_baby"):         # absent only in older timing builds
+            L.khb_build_baby.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                         C.c_uint64, P(C.c_uint64), P(C.c_uint64), P(C.c_uint32), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                         P(C.c_float)]
         L.khb_load_lane_offsets.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32]
         L.khb_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]
         L.khb_collect.argtypes = [C.c_void_p, P(Cand), C.c_uint32, P(Degenerate), C.c_uint32, P(Stats)]
@@ -143,6 +148,7 @@ def lib(path: str | None = None) -> C.CDLL:
     return _libs[path]
 
 
+KHB_EINVAL, KHB_ESTATE, KHB_EBUSY, KHB_EINCOMPLETE = -1, -5, -6, -7
 KHB_EHANDOFF = -8
 
 
@@ -156,7 +162,9 @@ def _check(rc: int, ctx=None, L: C.CDLL | None = None) -> None:
             msg += f" ({seen.value} of {total.value} waves)"
         elif ctx:
             msg += f" (hipError {L.khb_last_hip_error(ctx)})"
-        raise KhbError(f"khbsgs: {msg} [{rc}]")
+        err = KhbError(f"khbsgs: {msg} [{rc}]")
+        err.code = rc
+        raise err
 
 
 def build_info(path: str | None = None) -> dict:
@@ -295,6 +303,44 @@ class Engine:
         out = C.create_string_buffer(n)
         _check(self.L.khb_probe(self.h, xs, out, n), self.h, self.L)
         return out.raw
+
+    # ---- baby-step tables on the GPU ----
+    def build_baby(self, centres: bytes, groups_per_job: int, l1ext: int, m2: int, m3: int, geoms,
+                   want=("l1", "l2", "l3", "bp", "gate"), gate_log2: int = 0, gate_probes: int = 3,
+                   fill: int = 0) -> dict:
+        """khb_build_baby over the loaded Gn table and build offsets.  geoms: (bytes_per_sub, bits, hashes) of levels
+        1..3, None for a level that is not in `want`; want: which of "l1", "l2", "l3", "bp", "gate" to build (the
+        others go in as null pointers).  Every host buffer is filled with the byte `fill` before the call, so what
+        the call leaves untouched shows, and is followed by 64 guard bytes that must come back as they were.
+        Returns {"l1", "l2", "l3", "bp", "gate"} (bytes, or None when not wanted), "kernel_ms" and "incomplete" (True
+        when the library answered KHB_EINCOMPLETE: the buffers hold what a short walk wrote)."""
+        want = set(want)
+        if want - {"l1", "l2", "l3", "bp", "gate"}:
+            raise ValueError(f"build_baby: unknown outputs {sorted(want)}")
+        nb, bits, hashes = (C.c_uint64 * 3)(), (C.c_uint64 * 3)(), (C.c_uint32 * 3)()
+        sizes = {"bp": 16 * m3, "gate": (1 << gate_log2) // 8}
+        for l, g in enumerate(geoms):
+            if g is not None:
+                nb[l], bits[l], hashes[l] = g
+                sizes[f"l{l + 1}"] = 256 * g[0]
+            elif f"l{l + 1}" in want:
+                raise ValueError(f"build_baby: level {l + 1} wanted without a geometry")
+        guard = b"\x5a" * 64             # behind every buffer: the library must not write past what it was given
+        bufs = {k: C.create_string_buffer(bytes([fill]) * sizes[k] + guard, sizes[k] + len(guard)) if k in want
+                else None for k in ("l1", "l2", "l3", "bp", "gate")}
+        ms = C.c_float(0)
+        rc = self.L.khb_build_baby(self.h, centres, len(centres) // 64, groups_per_job, l1ext, m2, m3, nb, bits,
+                                   hashes, bufs["l1"], bufs["l2"], bufs["l3"], bufs["bp"], bufs["gate"], gate_log2,
+                                   gate_probes, C.byref(ms))
+        if rc != KHB_EINCOMPLETE:
+            _check(rc, self.h, self.L)
+        for k, b in bufs.items():
+            if b is not None and b.raw[sizes[k]:] != guard:
+                raise KhbError(f"khbsgs: khb_build_baby wrote past the {sizes[k]} bytes of {k}")
+        out = {k: b.raw[:sizes[k]] if b is not None else None for k, b in bufs.items()}
+        out["kernel_ms"] = float(ms.value)
+        out["incomplete"] = rc == KHB_EINCOMPLETE
+        return out
 
     # ---- resident level-1 bloom and gate (additions to ABI 7) ----
     def build_l1_resident(self, centres: bytes, groups_per_job: int, l1ext: int, bytes_per_sub: int, bits: int,
