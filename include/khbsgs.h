@@ -56,7 +56,9 @@ extern "C" {
  * khb_hash160 kind 3) is an addition of the same sort: new values of existing arguments, version 7; a caller that
  * needs it checks for KHB_SEARCH_ETH in this header, and a library without it answers KHB_EINVAL.  -m xpoint
  * (KHB_SEARCH_XPOINT, KHB_ADDR_KIND_X and khb_hash160 kind 4) likewise: new values of existing arguments, version 7;
- * a caller checks for KHB_SEARCH_XPOINT here, and a library without it answers KHB_EINVAL. */
+ * a caller checks for KHB_SEARCH_XPOINT here, and a library without it answers KHB_EINVAL.  -m vanity
+ * (khb_load_vanity, khb_vanity_match and KHB_SEARCH_VANITY) likewise: two added entry points and a new value of an
+ * existing argument, version 7; a caller checks for KHB_SEARCH_VANITY here or for the khb_load_vanity symbol. */
 #define KHB_ABI_VERSION 7
 int khb_abi_version(void);
 /* What this library was built as, one line of `key=value` words: abi, arch, variant ("product" for the in-tree
@@ -302,10 +304,16 @@ int khb_load_addr_bloom(khb_ctx* ctx, const uint8_t* bf, uint64_t bytes, uint64_
  * the first 20 bytes of each point's big-endian x are probed in the bloom (a bloom over such 20-byte values), with
  * -e also those of beta*x and beta^2*x; y is never computed.  Hits have kind KHB_ADDR_KIND_X | e << 2 and the host
  * confirms them with lambda^e * key, no sign fix-up.  With -l bits or KHB_SEARCH_ETH it is KHB_EINVAL and nothing is
- * queued. */
+ * queued.
+ * search & KHB_SEARCH_VANITY (-m vanity, keyhunt.cpp:3105-3540), OR'ed with the -l value 0/1/2 and optionally with
+ * KHB_SEARCH_ENDOMORPHISM: the same walk and hash160s as above, but every hash is tested against the interval table
+ * of khb_load_vanity instead of the bloom (no address bloom is needed), and every hash inside an interval is a hit,
+ * with the same kind = form | e << 2.  Combined with KHB_SEARCH_ETH or KHB_SEARCH_XPOINT it is KHB_EINVAL; without a
+ * loaded table KHB_ESTATE; nothing is queued in either case. */
 #define KHB_SEARCH_ENDOMORPHISM 4
 #define KHB_SEARCH_ETH 8
 #define KHB_SEARCH_XPOINT 16
+#define KHB_SEARCH_VANITY 32
 int khb_addr_submit(khb_ctx* ctx, const uint8_t* centres_xy_be, uint32_t n_jobs, uint32_t group_begin,
                     uint32_t group_count, int search);
 /* stats->n_cand = number of bloom hits (may exceed cap); giant_steps = keys scanned. */
@@ -320,6 +328,26 @@ int khb_addr_dump(khb_ctx* ctx, const uint8_t* centre_xy_be, uint32_t group_begi
  * probes them (x < p; y is not read), then one byte = bloom_check20 result against the
  * loaded address bloom (0 when none is loaded). */
 int khb_hash160(khb_ctx* ctx, int kind, const uint8_t* xy_be, uint8_t* out, uint32_t n);
+
+/* ---- -m vanity: address prefixes as ranges of hash160 values ----
+ * The table is n sorted, disjoint, closed intervals [lo_i, hi_i] of 160-bit big-endian numbers (20 bytes each,
+ * lo_i <= hi_i and hi_i < lo_(i+1); KHB_EINVAL otherwise or for n = 0).  The library builds a bucket bitmap of 2^16
+ * bits from them (bit b set iff some interval holds a value whose first two bytes are b) and uploads both.  A hash
+ * matches iff it lies in one of the intervals: the device tests its bucket's bit (the bitmap is in LDS) and only on a
+ * set bit binary-searches the lower bounds.
+ * The caller derives the intervals from address prefixes (libkhhost: a prefix "1..." gives, per address length, the
+ * range from the prefix padded with '1' to the prefix padded with 'z', cut to the 25-byte values with the prefix's
+ * number of leading zero bytes, without the four checksum bytes) and confirms every hit by the printed address, so
+ * the device's superset (wrong only at an interval's two ends, where the checksum decides) is made exact.
+ * One deliberate deviation: the reference's addvanity (keyhunt.cpp:5837-5958) pairs the j-th lower bound with the
+ * j-th upper bound of two lists that can differ in length, which drops or empties ranges (for "1Q" its 34-character
+ * addresses are never matched) and scans them linearly behind a bloom over their common leading bytes
+ * (keyhunt.cpp:5775-5801); neither is reproduced.  A load replaces the previous table; KHB_EBUSY while a submission
+ * is in flight. */
+int khb_load_vanity(khb_ctx* ctx, const uint8_t* lo_be20, const uint8_t* hi_be20, uint32_t n);
+/* self-test: hit[i] = 1 iff the 20-byte value h20[20 i ..] lies in an interval of the loaded table, through the
+ * scan kernels' own match (bitmap copied to LDS, then vanity_match).  KHB_ESTATE before khb_load_vanity. */
+int khb_vanity_match(khb_ctx* ctx, const uint8_t* h20, uint8_t* hit, uint32_t n);
 
 /* ---- baby-step tables on the GPU (thread_bPload, keyhunt.cpp:4404-4592; orchestration 1615-1880) ----
  * Uses the loaded giant table as Gn[i] = (i+1)*G, _2Gn = 1024*G and the lane offsets for jobs of

@@ -23,8 +23,10 @@ extern "C" {
  * ABI 8 added -m address -c eth: khh_addr_new_eth, khh_addr_skipped, khh_eth_address, search = KHB_SEARCH_ETH and
  * khh_addr_confirm's kind KHB_ADDR_KIND_ETH.
  * ABI 9 added -m xpoint: khh_addr_new_xpoint, khh_addr_counted, search = KHB_SEARCH_XPOINT (optionally with
- * KHB_SEARCH_ENDOMORPHISM) and khh_addr_confirm's kinds KHB_ADDR_KIND_X | e << 2. */
-#define KHH_ABI_VERSION 9
+ * KHB_SEARCH_ENDOMORPHISM) and khh_addr_confirm's kinds KHB_ADDR_KIND_X | e << 2.
+ * ABI 10 added -m vanity: khh_addr_new_vanity, khh_addr_vanity_intervals, khh_addr_vanity_match and
+ * khh_vanity_target_ok. */
+#define KHH_ABI_VERSION 10
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -187,6 +189,32 @@ khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t
  * other handle ever with it: the mismatch is an error return with a message, as for -c eth. */
 khh_addr* khh_addr_new_xpoint(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                               uint32_t gpl, int threads, char* err, size_t errlen);
+/* -m vanity: text holds one address prefix per line (trimmed of " \t\n\r"; blank lines are passed over).  A target
+ * is accepted iff it is valid Base58, 1 to 29 characters long, begins with '1' and yields at least one interval; every
+ * other line is skipped (khh_addr_skipped).  A hash160 matches a target iff its P2PKH address begins with it.  Each
+ * target becomes, per address length, the range from the target padded with '1' to the target padded with 'z', cut to
+ * the 25-byte values with the target's number of leading zero bytes (a target of '1' characters alone: at least that
+ * many) and shifted right by 32 bits to drop the checksum; the ranges of all targets are merged into sorted, disjoint
+ * intervals (touching ones joined), the table khb_load_vanity takes.  The device reports every hash inside them and
+ * khh_addr_confirm / the search keep a hit only if the recovered key's address begins with a target, so the found
+ * set is exact.
+ * Deliberate deviations from the reference: its addvanity (keyhunt.cpp:5837-5958) pairs the j-th '1'-padded bound
+ * with the j-th 'z'-padded bound of two lists that can differ in length, which loses ranges (for "1Q" the 34-character
+ * addresses are never matched); the intervals here are exact.  And it accepts targets that do not begin with '1'
+ * ("3abc") and then matches P2PKH hashes whose printed address does not carry the prefix; they are rejected here.
+ * Such a handle is searched with search = 0, 1 or 2 (-l), optionally OR'ed with KHB_SEARCH_ENDOMORPHISM; the search
+ * adds KHB_SEARCH_VANITY itself.  A handle without an accepted target can be inspected; searching it is KHB_EINVAL
+ * (the Python binding does not hand out such a handle: khhost.Addr raises ValueError when the library counted none).
+ * It has no bloom and no 20-byte table (khh_addr_table gives n = 0). */
+khh_addr* khh_addr_new_vanity(const char* text, const uint8_t stride_be[32], uint64_t n_seq, uint32_t gpl, int threads,
+                              char* err, size_t errlen);
+/* The merged intervals of a vanity handle: *n entries of lo || hi (20 bytes each, big-endian), ascending. */
+const uint8_t* khh_addr_vanity_intervals(const khh_addr* a, uint64_t* n);
+/* For n 20-byte hash160 values on a vanity handle: out[i] bit 0 = the value lies in a merged interval (what the device
+ * reports), bit 1 = its address begins with an accepted target (what the confirmation keeps). */
+int khh_addr_vanity_match(const khh_addr* a, const uint8_t* h20, uint8_t* out, uint64_t n);
+/* 1 when s would be accepted as a vanity target, 0 when not ("was NOT Added"). */
+int khh_vanity_target_ok(const char* s);
 void khh_addr_free(khh_addr* a);
 /* lines the loader omitted ("[I] Ommiting invalid line") */
 uint64_t khh_addr_skipped(const khh_addr* a);
@@ -201,7 +229,11 @@ uint32_t khh_addr_lane_offsets(const khh_addr* a, uint8_t* out /* n*64, may be N
  * KHB_SEARCH_ENDOMORPHISM (4, include/khbsgs.h) for -e: the found keys are then lambda^e multiples too; or with
  * search = KHB_SEARCH_ETH (8) alone on a khh_addr_new_eth handle: found keys come back with compressed = 0 and the
  * 20 address bytes in rmd; or with search = KHB_SEARCH_XPOINT (16), alone or with KHB_SEARCH_ENDOMORPHISM, on a
- * khh_addr_new_xpoint handle: compressed = 0 and the matched first 20 bytes of x in rmd.  Found keys
+ * khh_addr_new_xpoint handle: compressed = 0 and the matched first 20 bytes of x in rmd; or with search 0/1/2,
+ * optionally with KHB_SEARCH_ENDOMORPHISM, on a khh_addr_new_vanity handle: every key in the range (with -e also its
+ * lambda multiples, and n - key as the forms imply) whose address begins with a target; the search goes on after a
+ * match, and a launch is sized from the targets' share of all hashes so that its expected hits stay at or below a
+ * quarter of the hit ring.  Found keys
  * (32 B BE each) with compressed flags and rmd160s, in discovery order; *n_found may exceed cap.
  * Discovery order is batch order, and (chunk, key) order inside a batch, except after an overflow: a batch
  * whose bloom hits overflowed khb_addr_hit_capacity is rescanned in parts queued behind the batch already
@@ -228,7 +260,8 @@ int khh_addr_set_hit_capacity(khh_addr* a, uint32_t cap);
  * hash is a target, 0 when it is not.  kind KHB_ADDR_KIND_ETH (keyhunt.cpp:2989-3002): the ETH address of key*G
  * is looked up and the key returned unchanged.  kind KHB_ADDR_KIND_X | e << 2 (keyhunt.cpp:3005-3062): the first 20
  * bytes of beta^e * x(key*G) are looked up and lambda^e * key mod n returned (the key itself for e = 0), never
- * negated, compressed = 0. */
+ * negated, compressed = 0.  On a vanity handle: the BTC kinds and recovery, and 1 only if the address of the
+ * recovered key's hash160 begins with an accepted target. */
 int khh_addr_confirm(const khh_addr* a, const uint8_t key_be[32], uint32_t kind, uint8_t out_key_be[32],
                      int* compressed);
 /* hash160 of a public key (x||y BE) and its P2PKH address (out_addr >= 36 bytes) */

@@ -86,6 +86,10 @@ struct khb_ctx {
   // -m address
   uint8_t* d_abloom = nullptr;
   khb::BloomGeom ageom{};
+  // -m vanity (khb_load_vanity): van_n intervals as lo words [5 van_n], hi words [5 van_n], then the bucket bitmap
+  // (kVanityBitmapWords words), one allocation; null = none loaded
+  uint32_t* d_van = nullptr;
+  uint32_t van_n = 0;
   // second / third check (khb_load_check_tables, khb_check): tables, a high-priority stream of its own
   // and buffers grown to the largest batch
   khb::CheckTables ck{};

@@ -5,8 +5,32 @@
 #include "hash160.hpp"
 #include "keccak.hpp"
 #include "xpoint.hpp"
+#include "vanity.hpp"
 
 namespace khbk {
+
+// The vanity kernels' copy of the bucket bitmap in LDS (8 KiB per block; only kernels that reach it allocate it).
+__device__ __forceinline__ uint32_t* vanity_lds() {
+  __shared__ uint32_t s_bitmap[kVanityBitmapWords];
+  return s_bitmap;
+}
+
+// Kernel entry of a vanity instance: every block copies the bitmap in once (the grid is persistent), one barrier.
+__device__ __forceinline__ void vanity_load_bitmap(const uint32_t* __restrict__ bitmap) {
+  uint32_t* s = vanity_lds();
+  for (uint32_t i = threadIdx.x; i < kVanityBitmapWords; i += blockDim.x) s[i] = bitmap[i];
+  __syncthreads();
+}
+
+// The last step of a BTC address mode: is the hash160 h a candidate?  The -m address modes probe the target bloom;
+// the -m vanity modes test the interval table (device/vanity.hpp), its bitmap in LDS.
+template <int MODE>
+__device__ __forceinline__ bool addr_match(const ScanArgs& A, const uint32_t h[5]) {
+  if constexpr (is_vanity(MODE))
+    return vanity_match(vanity_lds(), A.van_lo, A.van_hi, A.van_n, h);
+  else
+    return bloom_check20(A.bloom, A.geom, h);
+}
 
 // beta (keyhunt.cpp:584): lambda*P = (beta*x, y).  beta^2*x is computed as beta*(beta*x), the same canonical value as
 // the reference's ModMulK1(x, beta2) (beta2 = beta^2 mod p, keyhunt.cpp:585), with one constant and no indexed table.
@@ -55,8 +79,8 @@ __device__ __forceinline__ void xpoint_probe(const ScanArgs& A, const Fe& x1, ui
 
 // -m address handling of one point (keyhunt.cpp:2716-2937, BTC, no endomorphism): hash160 of
 // the compressed key for both prefixes from x alone (covers +k and -k, keyhunt.cpp:2719-2733) and/or
-// of the uncompressed key, each probed in the single target bloom; hits go to the host, which runs
-// searchbinary and the key recovery.  x and y are canonical.
+// of the uncompressed key, each probed in the single target bloom (-m vanity: tested against the interval table,
+// addr_match); hits go to the host, which runs searchbinary and the key recovery.  x and y are canonical.
 template <int MODE>
 __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const Fe& y, uint32_t job, uint32_t j,
                                            uint32_t t) {
@@ -96,7 +120,7 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
 #pragma unroll 1
           for (uint32_t pre = 2; pre <= 3; ++pre) {
             hash160_compressed(h, pre, xe);
-            if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, (pre - 2) | (e << 2));
+            if (addr_match<MODE>(A, h)) emit_ahit(A, job, j, t, (pre - 2) | (e << 2));
           }
         }
         if constexpr (addr_uncompressed(MODE)) {
@@ -107,21 +131,21 @@ __device__ __forceinline__ void addr_point(const ScanArgs& A, const Fe& x, const
 #pragma unroll
             for (int k = 0; k < 8; ++k) yy.v[k] = neg ? ny.v[k] : y.v[k];
             hash160_uncompressed(h, xe, yy);
-            if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, (2u + neg) | (e << 2));
+            if (addr_match<MODE>(A, h)) emit_ahit(A, job, j, t, (2u + neg) | (e << 2));
           }
         }
       }
     } else {
-      if constexpr (MODE == kAddrC || MODE == kAddrB) {
+      if constexpr (addr_compressed(MODE)) {
 #pragma unroll 1
         for (uint32_t pre = 2; pre <= 3; ++pre) {
           hash160_compressed(h, pre, x);
-          if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, pre - 2);
+          if (addr_match<MODE>(A, h)) emit_ahit(A, job, j, t, pre - 2);
         }
       }
-      if constexpr (MODE == kAddrU || MODE == kAddrB) {
+      if constexpr (addr_uncompressed(MODE)) {
         hash160_uncompressed(h, x, y);
-        if (bloom_check20(A.bloom, A.geom, h)) emit_ahit(A, job, j, t, 2);
+        if (addr_match<MODE>(A, h)) emit_ahit(A, job, j, t, 2);
       }
     }
   }

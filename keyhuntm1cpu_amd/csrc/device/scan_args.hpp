@@ -67,21 +67,33 @@ enum : int {
   kAddrEth = 13,   // -m address -c eth: Keccak-256 of x || y (keyhunt.cpp:2776-2780; device/keccak.hpp)
   kAddrX = 14,     // -m xpoint: the first 20 bytes of x probed as they are (keyhunt.cpp:3005-3062; device/xpoint.hpp)
   kAddrXE = 15,    // kAddrX with -e: x, beta*x and beta^2*x (keyhunt.cpp:3013-3043)
+  kVanU = 16,      // -m vanity: kAddrU / kAddrC / kAddrB with the interval match of device/vanity.hpp in the place of
+  kVanC = 17,      //   the target bloom (KHB_SEARCH_VANITY)
+  kVanB = 18,
+  kVanUE = 19,     // -m vanity -e: kAddrUE / kAddrCE / kAddrBE likewise
+  kVanCE = 20,
+  kVanBE = 21,
 };
 constexpr bool is_gated(int m) { return m == kScanG || m == kScanG1 || m == kScanG2; }
 // filter stages in front of the full gate: 0 (kScanG), 1 (the fold, kScanG1), 2 (filter + fold, kScanG2)
 constexpr int gate_stages(int m) { return m == kScanG2 ? 2 : m == kScanG1 ? 1 : 0; }
 constexpr bool is_scan(int m) { return m == kScan || is_gated(m); }
-constexpr bool is_endo(int m) { return m >= kAddrUE && m <= kAddrBE; }       // BTC -e (kAddrXE is is_xpoint)
+constexpr bool is_vanity(int m) { return m >= kVanU && m <= kVanBE; }
+// BTC -e (kAddrXE is is_xpoint)
+constexpr bool is_endo(int m) { return (m >= kAddrUE && m <= kAddrBE) || (m >= kVanUE && m <= kVanBE); }
 constexpr bool is_xpoint(int m) { return m == kAddrX || m == kAddrXE; }
 constexpr bool is_addr(int m) {
-  return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth || is_xpoint(m);
+  return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth || is_xpoint(m) || is_vanity(m);
 }
-constexpr bool needs_y(int m) {
-  return m == kAddrU || m == kAddrB || m == kAddrDump || m == kAddrUE || m == kAddrBE || m == kAddrEth;
+constexpr bool addr_compressed(int m) {
+  return m == kAddrC || m == kAddrB || m == kAddrCE || m == kAddrBE || m == kVanC || m == kVanB || m == kVanCE ||
+         m == kVanBE;
 }
-constexpr bool addr_compressed(int m) { return m == kAddrC || m == kAddrB || m == kAddrCE || m == kAddrBE; }
-constexpr bool addr_uncompressed(int m) { return m == kAddrU || m == kAddrB || m == kAddrUE || m == kAddrBE; }
+constexpr bool addr_uncompressed(int m) {
+  return m == kAddrU || m == kAddrB || m == kAddrUE || m == kAddrBE || m == kVanU || m == kVanB || m == kVanUE ||
+         m == kVanBE;
+}
+constexpr bool needs_y(int m) { return addr_uncompressed(m) || m == kAddrDump || m == kAddrEth; }
 constexpr bool is_dump(int m) { return m == kDump || m == kAddrDump || m == kBaby; }
 constexpr bool is_batched(int m) { return is_scan(m) || m == kDump; }   // x only, kBatch groups per item (scan_batch)
 constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and y, group by group (scan_group)
@@ -101,8 +113,14 @@ constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and
 // spill, 184 and 192 B of scratch per lane (profiles/xpoint)
 #define KHB_ADDR_X_WAVES_PER_SIMD 3
 #endif
+#ifndef KHB_VANITY_WAVES_PER_SIMD
+// occupancy target of the -m vanity kernels: the address kernels'.  At 4 waves (128 VGPRs) every vanity instance
+// uses scratch as its address twin does, within 24 B per lane of it (228 to 412 B against 236 to 432 B)
+#define KHB_VANITY_WAVES_PER_SIMD KHB_ADDR_WAVES_PER_SIMD
+#endif
 constexpr int waves_per_simd(int m) {
   return m == kAddrEth ? KHB_ADDR_ETH_WAVES_PER_SIMD
+         : is_vanity(m) ? KHB_VANITY_WAVES_PER_SIMD
          : is_xpoint(m) ? KHB_ADDR_X_WAVES_PER_SIMD
          : is_endo(m)  ? KHB_ADDR_E_WAVES_PER_SIMD
          : is_addr(m)  ? KHB_ADDR_WAVES_PER_SIMD
@@ -166,6 +184,12 @@ struct ScanArgs {
   uint64_t job_keys;                   // baby steps per job
   uint64_t n_items;
   uint32_t n_jobs, group_begin, group_end, gpl, lanes_per_job, stride, cand_cap, degen_cap;
+  // -m vanity (khb_load_vanity; device/vanity.hpp): van_n sorted disjoint intervals, five words per bound with word 0
+  // the most significant, and the 2^16-bit bucket bitmap every block copies into LDS at kernel entry
+  const uint32_t* __restrict__ van_lo;
+  const uint32_t* __restrict__ van_hi;
+  const uint32_t* __restrict__ van_bitmap;
+  uint32_t van_n;
 };
 
 __device__ __forceinline__ void emit_cand(const ScanArgs& A, uint32_t job, uint32_t a) {

@@ -95,7 +95,7 @@ void eth_address_pub(const Pt& p, uint8_t out[20]) {
 // -------------------------------------------------------------------------------- base58
 static const char kB58[] = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
 
-static int b58_digit(unsigned char c) {
+int b58_digit(unsigned char c) {
   if (!c || (c & 0x80)) return -1;
   const char* p = strchr(kB58, c);
   return p ? (int)(p - kB58) : -1;
@@ -229,6 +229,13 @@ static bool line_h160(TargetKind kind, const std::string& aux, H160& h) {
 bool AddrTargets::load_text(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err,
                             TargetKind kind) {
   T = AddrTargets();
+  if (kind == kTargetsVanity) {          // no bloom and no table: the intervals of vanity_host.hpp
+    T.vanity = true;
+    T.van.load_text(text);
+    T.skipped = T.van.skipped;
+    T.counted = T.van.accepted.size();
+    return true;
+  }
   T.eth = kind == kTargetsEth;
   T.xpoint = kind == kTargetsXpoint;
   const std::vector<std::string> lines = fgets_lines(text, kind == kTargetsXpoint ? 1000 : 100);
@@ -381,14 +388,14 @@ bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound
   uint8_t h[20];
   if (form < 2) {
     hash160_x((uint8_t)(2 + form), P, h);
-    if (!T.searchbinary(h)) return false;
+    if (!T.is_target(h)) return false;
     uint8_t hc[20];
     hash160_pub(P, true, hc);
     out->key = memcmp(h, hc, 20) != 0 ? secp_order() - k : k;
     out->compressed = true;
   } else {
     hash160_pub(form == 2 ? P : negation(P), false, h);
-    if (!T.searchbinary(h)) return false;
+    if (!T.is_target(h)) return false;
     out->key = form == 2 ? k : secp_order() - k;
     out->compressed = false;
   }
@@ -483,7 +490,8 @@ struct AddrOps {
   int submit(const ABatch& b) {
     const int rc = khb_addr_submit(ctx, b.centres.data(), (uint32_t)b.bases.size(), b.group_begin,
                                    b.group_count ? b.group_count : groups,
-                                   S.cfg.search | (S.cfg.endomorphism ? KHB_SEARCH_ENDOMORPHISM : 0));
+                                   S.cfg.search | (S.cfg.endomorphism ? KHB_SEARCH_ENDOMORPHISM : 0) |
+                                       (S.T.vanity ? KHB_SEARCH_VANITY : 0));
     return rc ? fail(rc, "khb_addr_submit") : 0;
   }
   int collect() {
@@ -540,12 +548,20 @@ void device_loop(AddrShared& S, int device) {
   int rc = khb_open(device, S.cfg.lanes, &ctx);
   if (rc) { ops.fail(rc, "khb_open"); return; }
   const std::vector<uint8_t> gtab = S.G.table_be(), offs = S.G.offs_be();
-  const BloomGeom bg = S.T.bloom.geom();
+  const bool vanity = S.T.vanity;
+  const BloomGeom bg = vanity ? BloomGeom{} : S.T.bloom.geom();
+  const std::vector<uint8_t> iv = S.T.van.merged_bytes();   // lo || hi per interval
+  std::vector<uint8_t> van_lo(iv.size() / 2), van_hi(iv.size() / 2);
+  for (size_t i = 0; i < iv.size() / 40; ++i) {
+    memcpy(van_lo.data() + 20 * i, iv.data() + 40 * i, 20);
+    memcpy(van_hi.data() + 20 * i, iv.data() + 40 * i + 20, 20);
+  }
   int depth = 2;
   if ((S.cfg.hit_cap && (rc = khb_set_candidate_capacity(ctx, S.cfg.hit_cap))) ||
       (rc = khb_load_giant_table(ctx, gtab.data())) ||
       (rc = khb_load_lane_offsets(ctx, offs.data(), (uint32_t)S.G.offs.size(), S.G.gpl)) ||
-      (rc = khb_load_addr_bloom(ctx, S.T.bloom.bf.data(), bg.bytes_per_sub, bg.bits, bg.hashes))) {
+      (rc = vanity ? khb_load_vanity(ctx, van_lo.data(), van_hi.data(), (uint32_t)(iv.size() / 40))
+                   : khb_load_addr_bloom(ctx, S.T.bloom.bf.data(), bg.bytes_per_sub, bg.bits, bg.hashes))) {
     ops.fail(rc, "table upload");
   } else if ((rc = reserve_depth(depth, KHB_ENOMEM, [&](int n) { return khb_reserve_slots(ctx, n); },
                                  [&](const char* m) {   // large targets or many devices' worth of scratch
@@ -561,6 +577,17 @@ void device_loop(AddrShared& S, int device) {
     ops.per_batch = std::min<uint64_t>(4096, std::max<uint64_t>(1, (8ull * khb_lanes(ctx) + lanes_per_job - 1) / lanes_per_job));
     ops.hits.resize(1u << 18);
     ops.acap = std::min<uint32_t>(khb_addr_hit_capacity(ctx), (uint32_t)ops.hits.size());
+    if (vanity) {
+      // every hash inside the table is a hit, so a launch is sized to keep its expected hits (keys x hashes per key x
+      // the table's share of all hashes) at or below a quarter of the ring; more than that in one chunk overflows
+      // and is rescanned in parts like any other overflow
+      // hashes per key: 1 uncompressed, 2 compressed (02 and 03), 3 for both; with -e 6, 6 and 12
+      const int hashes[2][3] = {{1, 2, 3}, {6, 6, 12}};
+      const double forms = hashes[S.cfg.endomorphism ? 1 : 0][S.cfg.search];
+      const double per_chunk = (double)S.cfg.n_seq * forms * S.T.van.covered();
+      const double fit = per_chunk > 0 ? 0.25 * ops.acap / per_chunk : (double)ops.per_batch;
+      ops.per_batch = fit < 1 ? 1 : std::min<uint64_t>(ops.per_batch, (uint64_t)fit);
+    }
     run_pipeline<ABatch>(ops, depth);
   }
   khb_close(ctx);
@@ -576,6 +603,12 @@ int addr_search(const AddrTargets& T, const AddrGen& G, const AddrConfig& cfg, c
   if (cfg.n_seq < 1024 || cfg.n_seq % 1024 || cfg.n_seq / 1024 > 0xFFFFFFFFull) {
     if (err) *err = "n must be a positive multiple of 1024";
     return -100;
+  }
+  if (T.vanity && (cfg.search < 0 || cfg.search > 2 || T.van.merged.empty())) {
+    if (err)
+      *err = T.van.merged.empty() ? "there are no vanity targets"
+                                  : "vanity targets are searched with search 0, 1 or 2 (-l), optionally with -e";
+    return KHB_EINVAL;
   }
   const bool eth = cfg.search == KHB_SEARCH_ETH, xpoint = cfg.search == KHB_SEARCH_XPOINT;
   if (eth != T.eth || xpoint != T.xpoint || (eth && cfg.endomorphism) ||

@@ -1,4 +1,4 @@
-// Host side of keyhunt's -m address / -m rmd160 (BTC P2PKH, with or without -e; -c eth) and -m xpoint modes on
+// Host side of keyhunt's -m address / -m rmd160 (BTC P2PKH, with or without -e; -c eth), -m xpoint and -m vanity modes on
 // libkhbsgs: target loading (forceReadFileAddress, keyhunt.cpp:6300-6358; forceReadFileAddressEth, 6374-6450;
 // forceReadFileXPoint, 6454-6552), the generator table
 // (init_generator, keyhunt.cpp:4386-4399), chunk claiming (thread_process, keyhunt.cpp:2546-2567),
@@ -14,11 +14,14 @@
 #include "bloom_host.hpp"
 #include "secp_host.hpp"
 #include "u256.hpp"
+#include "vanity_host.hpp"
 
 namespace khb {
 
 using H160 = std::array<uint8_t, 20>;
 
+// The value of a Base58 digit, -1 for any other character.
+int b58_digit(unsigned char c);
 // b58tobin into 25 bytes with keyhunt's acceptance rule (decoded size == 25, base58.c:39-112).
 bool b58decode25(const char* s, uint8_t out[25]);
 // rmd160toaddress_dst (keyhunt.cpp:2274-2284): base58check of 0x00 || rmd.
@@ -36,6 +39,7 @@ enum TargetKind {
   kTargetsBtc = 0,      // -m address / -m rmd160: base58 P2PKH addresses or 40-hex hash160 (forceReadFileAddress)
   kTargetsEth = 1,      // -c eth: 40-hex lines, with or without a two-character prefix (forceReadFileAddressEth)
   kTargetsXpoint = 2,   // -m xpoint: public keys or x coordinates (forceReadFileXPoint)
+  kTargetsVanity = 3,   // -m vanity: address prefixes, one per line (vanity_host.hpp)
 };
 
 struct AddrTargets {
@@ -45,6 +49,8 @@ struct AddrTargets {
   std::vector<std::string> skipped;    // "[I] Ommiting invalid line": the trimmed lines
   bool eth = false;                    // -c eth: the table holds ETH addresses (kTargetsEth)
   bool xpoint = false;                 // -m xpoint: the table holds the first 20 bytes of x (kTargetsXpoint)
+  bool vanity = false;                 // -m vanity: `van` holds the targets; table and bloom stay empty (kTargetsVanity)
+  VanityTargets van;
 
   // text: the target file's contents.  Returns false with *err on an unusable bloom.  counted = lines of more than 20
   // characters (BTC) or of 40 or more (ETH, xpoint), and that many lines are read from the top of the file.
@@ -60,6 +66,8 @@ struct AddrTargets {
   static bool load_file(const char* path, int bloom_multiplier, AddrTargets& out, std::string* err,
                         TargetKind kind = kTargetsBtc);
   bool searchbinary(const uint8_t h[20]) const;   // keyhunt.cpp:2311-2335, literal
+  // h is wanted: searchbinary, or for -m vanity the address of h begins with a target (VanityTargets::matches)
+  bool is_target(const uint8_t h[20]) const { return vanity ? van.matches(h) : searchbinary(h); }
 };
 
 struct AddrGen {
@@ -75,7 +83,8 @@ struct AddrGen {
 struct AddrConfig {
   int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300),
                                        // KHB_SEARCH_ETH (-c eth; the targets must be kTargetsEth's) or
-                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be kTargetsXpoint's)
+                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be kTargetsXpoint's).
+                                       // kTargetsVanity targets take 0, 1 or 2; the search adds KHB_SEARCH_VANITY
   bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and (BTC) negated points
   U256 start{1}, end{1};               // [start, end): n_range_start / n_range_end
   uint64_t n_seq = 1ull << 32;         // keys per claimed chunk (-n, N_SEQUENTIAL_MAX)
@@ -110,7 +119,8 @@ struct AddrCallbacks {
 
 // Confirm one GPU bloom hit (khb_addr_hit.kind = form | e << 2) of the point whose key is `key`: searchbinary of the
 // hash the kind names, then the reference's key recovery (keyhunt.cpp:2789-2937): lambda^e * key, negated when the
-// hit is the other point of the pair.  False when the hash is not a target (a bloom false positive).
+// hit is the other point of the pair.  False when the hash is not a target (a bloom false positive).  With -m vanity
+// targets the same kinds and recovery, and the hash is a target iff its address begins with one of them.
 // kind KHB_ADDR_KIND_ETH (-c eth, keyhunt.cpp:2989-3002): the ETH address of key*G, the key returned unchanged.
 // kind KHB_ADDR_KIND_X | e << 2 (-m xpoint, keyhunt.cpp:3005-3062): the first 20 bytes of beta^e * x(key*G); the key
 // returned is lambda^e * key mod n (the walked key itself for e = 0), never negated; compressed = false.

@@ -22,6 +22,7 @@ struct khh_addr {
   AddrGen G;
   uint64_t n_seq = 0;
   uint32_t hit_cap = 0;      // tests: bloom-hit ring capacity per launch (0 = library default)
+  std::vector<uint8_t> van_bytes;   // khh_addr_vanity_intervals: lo || hi of the merged intervals
 };
 
 static void set_err(char* err, size_t n, const std::string& m) {
@@ -413,6 +414,7 @@ static khh_addr* addr_new(TargetKind kind, const char* text, int bloom_multiplie
   }
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   a->n_seq = n_seq;
+  a->van_bytes = a->T.van.merged_bytes();
   a->G.build(stride, (uint32_t)(n_seq / 1024), gpl ? gpl : 16, threads);
   return a;
 }
@@ -430,6 +432,30 @@ khh_addr* khh_addr_new_eth(const char* text, int bloom_multiplier, const uint8_t
 khh_addr* khh_addr_new_xpoint(const char* text, int bloom_multiplier, const uint8_t stride_be[32], uint64_t n_seq,
                               uint32_t gpl, int threads, char* err, size_t errlen) {
   return addr_new(kTargetsXpoint, text, bloom_multiplier, stride_be, n_seq, gpl, threads, err, errlen);
+}
+
+khh_addr* khh_addr_new_vanity(const char* text, const uint8_t stride_be[32], uint64_t n_seq, uint32_t gpl, int threads,
+                              char* err, size_t errlen) {
+  return addr_new(kTargetsVanity, text, 1, stride_be, n_seq, gpl, threads, err, errlen);
+}
+
+const uint8_t* khh_addr_vanity_intervals(const khh_addr* a, uint64_t* n) {
+  if (n) *n = a ? a->van_bytes.size() / 40 : 0;
+  return a && !a->van_bytes.empty() ? a->van_bytes.data() : nullptr;
+}
+
+int khh_addr_vanity_match(const khh_addr* a, const uint8_t* h20, uint8_t* out, uint64_t n) {
+  if (!a || !a->T.vanity || !h20 || !out) return KHB_EINVAL;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint8_t* h = h20 + 20 * i;
+    out[i] = (uint8_t)((a->T.van.in_table(h) ? 1 : 0) | (a->T.van.matches(h) ? 2 : 0));
+  }
+  return KHB_OK;
+}
+
+int khh_vanity_target_ok(const char* s) {
+  std::vector<VanityInterval> iv;
+  return s && VanityTargets::intervals_of(s, iv) ? 1 : 0;
 }
 
 uint64_t khh_addr_counted(const khh_addr* a) { return a ? a->T.counted : 0; }

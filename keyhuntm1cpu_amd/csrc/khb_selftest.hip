@@ -76,6 +76,20 @@ __global__ void k_x_be20(const Fe* __restrict__ xy, const uint8_t* __restrict__ 
   o[20] = bloom ? (bloom_check20(bloom, g, h) ? 1 : 0) : 0;
 }
 
+// khb_vanity_match: the vanity kernels' match stage on caller-supplied 20-byte values, the bitmap in LDS as there.
+// h: five words per value in hash160_*'s order (their little-endian bytes are the value's bytes).
+__global__ __launch_bounds__(256) void k_vanity_match(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
+                                                      const uint32_t* __restrict__ bitmap, uint32_t n_iv,
+                                                      const uint32_t* __restrict__ h, uint8_t* __restrict__ hit,
+                                                      uint32_t n) {
+  vanity_load_bitmap(bitmap);            // every lane of the block reaches the barrier
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[5];
+  for (int k = 0; k < 5; ++k) w[k] = h[5 * (size_t)i + k];
+  hit[i] = vanity_match(vanity_lds(), lo, hi, n_iv, w) ? 1 : 0;
+}
+
 // khb_dump_x (kind 1: x of every point of the bsgs walk, 32 bytes each) and khb_addr_dump (kind 2: x||y of the
 // address walk, 64 bytes each) of one job's groups.
 int dump_points(khb_ctx* c, int kind, const uint8_t* centre, uint32_t group_begin, uint32_t group_count,
@@ -156,6 +170,23 @@ int khb_probe(khb_ctx* c, const uint8_t* xs, uint8_t* hit, uint32_t n) {
   KHB_TRY(c, dh.alloc(n));
   KHB_TRY(c, hipMemcpy(d, h.data(), sizeof(Fe) * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, S.stream, c->d_bloom, c->geom, d, dh, n);
+  if (const int rc = sync_launch(c, S.stream)) return rc;
+  KHB_TRY(c, hipMemcpy(hit, dh, n, hipMemcpyDeviceToHost));
+  return KHB_OK;
+}
+
+int khb_vanity_match(khb_ctx* c, const uint8_t* h20, uint8_t* hit, uint32_t n) {
+  if (!c || !h20 || !hit || n == 0) return KHB_EINVAL;
+  if (!c->d_van) return KHB_ESTATE;
+  KHB_TRY(c, hipSetDevice(c->device));
+  Slot& S = c->slot[0];
+  DevBuf<uint32_t> d;                    // 20 bytes per value: on a little-endian host already hash160_*'s words
+  DevBuf<uint8_t> dh;
+  KHB_TRY(c, d.alloc(5 * (size_t)n));
+  KHB_TRY(c, dh.alloc(n));
+  KHB_TRY(c, hipMemcpy(d, h20, 20 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_vanity_match, dim3((n + 255) / 256), dim3(256), 0, S.stream, c->d_van,
+                     c->d_van + 5 * (size_t)c->van_n, c->d_van + 10 * (size_t)c->van_n, c->van_n, d.p, dh.p, n);
   if (const int rc = sync_launch(c, S.stream)) return rc;
   KHB_TRY(c, hipMemcpy(hit, dh, n, hipMemcpyDeviceToHost));
   return KHB_OK;

@@ -247,6 +247,37 @@ int khb_load_addr_bloom(khb_ctx* c, const uint8_t* bf, uint64_t bytes, uint64_t 
   return load_bloom(c, c->d_abloom, c->ageom, bf, bytes, bytes, bits, hashes);
 }
 
+// The -m vanity interval table (device/vanity.hpp): one allocation of lo words, hi words and the bucket bitmap.
+int khb_load_vanity(khb_ctx* c, const uint8_t* lo_be20, const uint8_t* hi_be20, uint32_t n) {
+  if (!c || !lo_be20 || !hi_be20 || n == 0) return KHB_EINVAL;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (memcmp(lo_be20 + 20 * (size_t)i, hi_be20 + 20 * (size_t)i, 20) > 0) return KHB_EINVAL;
+    if (i + 1 < n && memcmp(hi_be20 + 20 * (size_t)i, lo_be20 + 20 * (size_t)(i + 1), 20) >= 0) return KHB_EINVAL;
+  }
+  if (c->queued) return KHB_EBUSY;
+  KHB_TRY(c, hipSetDevice(c->device));
+  std::vector<uint32_t> h;
+  if (!host_alloc(h, 10 * (size_t)n + kVanityBitmapWords)) return KHB_ENOMEM;
+  uint32_t* lo = h.data();
+  uint32_t* hi = lo + 5 * (size_t)n;
+  for (size_t k = 0; k < 5 * (size_t)n; ++k) {
+    const uint8_t *a = lo_be20 + 4 * k, *b = hi_be20 + 4 * k;
+    lo[k] = ((uint32_t)a[0] << 24) | ((uint32_t)a[1] << 16) | ((uint32_t)a[2] << 8) | a[3];
+    hi[k] = ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3];
+  }
+  vanity_build_bitmap(hi + 5 * (size_t)n, lo, hi, n);
+  uint32_t* d = nullptr;
+  KHB_TRY(c, hipMalloc(&d, sizeof(uint32_t) * h.size()));
+  if (const hipError_t e = hipMemcpy(d, h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice)) {
+    hipFree(d);
+    return hip_fail(c, e);
+  }
+  hipFree(c->d_van);
+  c->d_van = d;
+  c->van_n = n;
+  return KHB_OK;
+}
+
 int khb_load_giant_table(khb_ctx* c, const uint8_t* gsn) {
   if (!c || !gsn) return KHB_EINVAL;
   if (c->queued) return KHB_EBUSY;

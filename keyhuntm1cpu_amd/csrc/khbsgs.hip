@@ -264,19 +264,26 @@ namespace {
 
 // khb_submit (kind 1: -m bsgs over the level-1 bloom, kBatch groups per item on the per-group offsets) and
 // khb_addr_submit (kind 2: -m address over the address bloom, gpl groups per item, hits in the slot's h_ahits;
-// `search` selects the kernel, BTC hash160, -c eth or -m xpoint, and is not read for kind 1).
+// `search` selects the kernel, BTC hash160, -c eth, -m xpoint or -m vanity, and is not read for kind 1).
 int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, uint32_t group_begin,
                 uint32_t group_count, int search) {
   const bool bsgs = kind == 1;
   int rc = check_scan_args(c, centres, n_jobs, group_begin, group_count, bsgs);
   if (rc) return rc;
+  // -m vanity: the BTC kernels (-l bits, optionally -e) over the interval table; with -c eth or -m xpoint it is
+  // KHB_EINVAL (khbsgs.h)
+  const bool vanity = !bsgs && search >= 0 && (search & KHB_SEARCH_VANITY);
+  if (vanity) {
+    search &= ~KHB_SEARCH_VANITY;
+    if (search & (KHB_SEARCH_ETH | KHB_SEARCH_XPOINT)) return KHB_EINVAL;
+  }
   const bool eth = !bsgs && search == KHB_SEARCH_ETH;     // exactly: no -l bits, no -e (khbsgs.h)
   // -m xpoint: alone or with -e; with -l bits or -c eth it is KHB_EINVAL (khbsgs.h)
   const bool xpoint = !bsgs && search >= 0 && (search & ~KHB_SEARCH_ENDOMORPHISM) == KHB_SEARCH_XPOINT;
   const bool endo = !bsgs && !eth && search >= 0 && (search & KHB_SEARCH_ENDOMORPHISM);
   if (endo) search &= ~KHB_SEARCH_ENDOMORPHISM;
   if (!bsgs && !eth && !xpoint && (search < 0 || search > 2)) return KHB_EINVAL;
-  if (!(bsgs ? c->d_bloom : c->d_abloom)) return KHB_ESTATE;
+  if (!(bsgs ? (void*)c->d_bloom : vanity ? (void*)c->d_van : (void*)c->d_abloom)) return KHB_ESTATE;
   if (c->queued && c->slot[c->head].kind != kind) return KHB_EBUSY;     // a scan of the other kind is in flight
   KHB_TRY(c, hipSetDevice(c->device));
   Slot* Sp = next_slot(c, rc);
@@ -296,6 +303,12 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
     A.geom = c->ageom;
     A.ahits = S.h_ahits;
     A.ahit_cap = khb_addr_hit_capacity(c);
+    if (vanity) {
+      A.van_lo = c->d_van;
+      A.van_hi = c->d_van + 5 * (size_t)c->van_n;
+      A.van_bitmap = c->d_van + 10 * (size_t)c->van_n;
+      A.van_n = c->van_n;
+    }
   }
   pts_from_be(S.h_centres, centres, n_jobs);
   const uint32_t blocks = c->lanes / kBlock;
@@ -307,6 +320,9 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
     launch_addr_eth(blocks, S.stream, A);
   else if (xpoint)
     launch_addr_x(endo ? kAddrXE : kAddrX, blocks, S.stream, A);
+  else if (vanity)
+    launch_vanity(endo ? (search == 0 ? kVanUE : search == 1 ? kVanCE : kVanBE)
+                       : (search == 0 ? kVanU : search == 1 ? kVanC : kVanB), blocks, S.stream, A);
   else if (endo)
     launch_addr_e(search == 0 ? kAddrUE : search == 1 ? kAddrCE : kAddrBE, blocks, S.stream, A);
   else
@@ -395,6 +411,7 @@ const char* khb_build_info(void) {
          " waves_per_simd=" KHB_STR(KHB_WAVES_PER_SIMD) " addr_waves_per_simd=" KHB_STR(KHB_ADDR_WAVES_PER_SIMD)
          " addr_eth_waves_per_simd=" KHB_STR(KHB_ADDR_ETH_WAVES_PER_SIMD)
          " addr_x_waves_per_simd=" KHB_STR(KHB_ADDR_X_WAVES_PER_SIMD)
+         " vanity_waves_per_simd=" KHB_STR(KHB_VANITY_WAVES_PER_SIMD)
          " batch=" KHB_STR(KHB_BATCH) " gate1=" KHB_STR(KHB_GATE1) " half_stream=" KHB_STR(KHB_HALF_STREAM)
          " gate0=" KHB_STR(KHB_GATE0) " defines=" KHB_BUILD_DEFINES " compiler=" __clang_version__;
 }
@@ -505,6 +522,7 @@ int khb_close(khb_ctx* c) {
   hipFree(c->d_offs);
   hipFree(c->d_gofs);
   hipFree(c->d_abloom);
+  hipFree(c->d_van);
   delete c;
   return KHB_OK;
 }

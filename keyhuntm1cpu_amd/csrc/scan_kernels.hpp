@@ -83,6 +83,7 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(MODE)) void k_giant_scan(Sca
   const uint32_t wave = QUEUE ? threadIdx.x >> 6 : 0;
   ProbeQueue Q{s_queue[wave], (volatile __attribute__((address_space(3))) uint32_t*)&s_count[wave]};
   if (QUEUE) *Q.n = 0;
+  if constexpr (is_vanity(MODE)) vanity_load_bitmap(A.van_bitmap);   // before any lane leaves: it ends in a barrier
   uint32_t walked = 0;     // groups this lane walked (count_walked: the host checks the launch's total)
   // Dynamic work items: each wave takes the next 64 items from a launch-wide counter
   // (counters[2], zeroed per launch), so a wave that runs ahead keeps taking work and every SIMD
@@ -125,6 +126,7 @@ void launch_addr(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& 
 void launch_addr_e(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrUE, kAddrCE, kAddrBE
 void launch_addr_eth(uint32_t blocks, hipStream_t stream, const ScanArgs& A);         // kAddrEth
 void launch_addr_x(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrX, kAddrXE
+void launch_vanity(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kVanU ... kVanBE
 void launch_baby(uint32_t blocks, hipStream_t stream, const ScanArgs& A);             // kBaby
 
 }  // namespace khbk

@@ -63,6 +63,7 @@ TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsg
 FIELD_OP_RAW = 0x100                                             # include/khbsgs.h KHB_FIELD_OP_RAW
 SEARCH_ENDOMORPHISM, SEARCH_ETH, ADDR_KIND_ETH = 4, 8, 16        # include/khbsgs.h KHB_SEARCH_*, KHB_ADDR_KIND_ETH
 SEARCH_XPOINT, ADDR_KIND_X = 16, 32                              # KHB_SEARCH_XPOINT, KHB_ADDR_KIND_X (| e << 2)
+SEARCH_VANITY = 32                                               # KHB_SEARCH_VANITY (| -l value, optionally | -e)
 
 
 def lib(path: str | None = None) -> C.CDLL:
@@ -141,6 +142,9 @@ def lib(path: str | None = None) -> C.CDLL:
                                     P(AddrHit), C.c_uint32, P(Stats)]
         L.khb_addr_dump.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p]
         L.khb_hash160.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32]
+        if hasattr(L, "khb_load_vanity"):        # the -m vanity additions to ABI 7
+            L.khb_load_vanity.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
+            L.khb_vanity_match.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
         if hasattr(L, "khb_check"):              # ABI 5
             L.khb_load_check_tables.argtypes = [C.c_void_p, P(CheckTables)]
             L.khb_check.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, P(CheckIn), C.c_uint32, P(CheckOut)]
@@ -389,13 +393,28 @@ class Engine:
 
     def addr_scan(self, centres: bytes, group_begin: int, group_count: int, search: int = 2, cap: int = 1 << 18):
         """Bloom hits [(job, group, t, kind)] of -m address over group_count groups of each job (search: 0/1/2,
-        | SEARCH_ENDOMORPHISM, SEARCH_ETH, or SEARCH_XPOINT optionally | SEARCH_ENDOMORPHISM)."""
+        | SEARCH_ENDOMORPHISM, SEARCH_ETH, or SEARCH_XPOINT optionally | SEARCH_ENDOMORPHISM; | SEARCH_VANITY on the
+        -l values: every hash inside the table of load_vanity is a hit)."""
         hits = (AddrHit * cap)()
         st = Stats()
         _check(self.L.khb_addr_scan(self.h, centres, len(centres) // 64, group_begin, group_count, search, hits, cap,
                                     C.byref(st)), self.h, self.L)
         n = min(st.n_cand, cap)
         return [(int(hits[i].job), int(hits[i].group), int(hits[i].t), int(hits[i].kind)) for i in range(n)], st
+
+    # ---- -m vanity ----
+    def load_vanity(self, intervals) -> None:
+        """The interval table of -m vanity: [(lo, hi)] of 20-byte big-endian bounds, sorted and disjoint."""
+        lo = b"".join(bytes(a) for a, _ in intervals)
+        hi = b"".join(bytes(b) for _, b in intervals)
+        _check(self.L.khb_load_vanity(self.h, lo, hi, len(intervals)), self.h, self.L)
+
+    def vanity_match(self, h20: bytes) -> bytes:
+        """One byte per 20-byte value: 1 iff it lies in an interval of the loaded table (the kernels' own match)."""
+        n = len(h20) // 20
+        out = C.create_string_buffer(n)
+        _check(self.L.khb_vanity_match(self.h, bytes(h20), out, n), self.h, self.L)
+        return out.raw
 
     def addr_dump(self, centre: bytes, group_begin: int, group_count: int) -> bytes:
         out = C.create_string_buffer(group_count * KHB_GROUP * 64)

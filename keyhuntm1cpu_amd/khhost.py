@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 9                 # include/khhost.h
+KHH_ABI_VERSION = 10                # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
 KHH_RESIDENT_INFO = 8
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
@@ -101,6 +101,13 @@ def lib() -> C.CDLL:
         L.khh_addr_new_eth.argtypes = L.khh_addr_new.argtypes
         L.khh_addr_new_xpoint.restype = C.c_void_p
         L.khh_addr_new_xpoint.argtypes = L.khh_addr_new.argtypes
+        L.khh_addr_new_vanity.restype = C.c_void_p
+        L.khh_addr_new_vanity.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p,
+                                          C.c_size_t]
+        L.khh_addr_vanity_intervals.restype = P(C.c_uint8)
+        L.khh_addr_vanity_intervals.argtypes = [C.c_void_p, P(C.c_uint64)]
+        L.khh_vanity_target_ok.argtypes = [C.c_char_p]
+        L.khh_addr_vanity_match.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64]
         L.khh_addr_counted.restype = C.c_uint64
         L.khh_addr_counted.argtypes = [C.c_void_p]
         L.khh_addr_free.argtypes = [C.c_void_p]
@@ -469,23 +476,41 @@ def eth_address(xy: bytes) -> bytes:
     return out.raw
 
 
+def vanity_target_ok(s: str) -> bool:
+    """Whether -m vanity accepts the target s: valid Base58, 1 to 29 characters, begins with '1', has an interval."""
+    return bool(lib().khh_vanity_target_ok(s.encode()))
+
+
 class Addr:
     """-m address targets (a target file's text) + generator for chunks of n_seq keys.  crypto="eth": the text is
     read as -c eth reads it (ETH addresses) and the handle is searched with KHB_SEARCH_ETH.  mode="xpoint": the text
-    is read as -m xpoint reads it (x values and public keys) and the handle is searched with KHB_SEARCH_XPOINT."""
+    is read as -m xpoint reads it (x values and public keys) and the handle is searched with KHB_SEARCH_XPOINT.
+    mode="vanity": the text holds one address prefix per line and the handle is searched with search 0, 1 or 2
+    (optionally | 4) for every key whose address begins with one of them; a text without an accepted target is a
+    ValueError."""
 
     def __init__(self, text: str, n_seq: int = 1 << 32, stride: int = 1, gpl: int = 16, bloom_multiplier: int = 1,
                  threads: int = 0, crypto: str = "btc", mode: str = "address"):
         if crypto not in ("btc", "eth"):
             raise ValueError("crypto: btc or eth")
-        if mode not in ("address", "xpoint"):
-            raise ValueError("mode: address or xpoint")
-        if mode == "xpoint" and crypto == "eth":
-            raise ValueError("mode xpoint has no crypto eth")
+        if mode not in ("address", "xpoint", "vanity"):
+            raise ValueError("mode: address, xpoint or vanity")
+        if mode != "address" and crypto == "eth":
+            raise ValueError(f"mode {mode} has no crypto eth")
         err = C.create_string_buffer(256)
-        new = (lib().khh_addr_new_xpoint if mode == "xpoint"
-               else lib().khh_addr_new_eth if crypto == "eth" else lib().khh_addr_new)
-        self.h = new(text.encode(), bloom_multiplier, _b32(stride), n_seq, gpl, threads, err, 256)
+        if mode == "vanity":
+            self.h = lib().khh_addr_new_vanity(text.encode(), _b32(stride), n_seq, gpl, threads, err, 256)
+            # the binding's rule, by the library's own count: a vanity handle without an accepted target can only
+            # be inspected in C, never searched, so the binding treats such a text as a bad argument
+            if self.h and not lib().khh_addr_counted(self.h):
+                lib().khh_addr_free(self.h)
+                self.h = None
+                raise ValueError("mode vanity: the text holds no target that is accepted (valid Base58, 1 to 29 "
+                                 "characters, beginning with '1')")
+        else:
+            new = (lib().khh_addr_new_xpoint if mode == "xpoint"
+                   else lib().khh_addr_new_eth if crypto == "eth" else lib().khh_addr_new)
+            self.h = new(text.encode(), bloom_multiplier, _b32(stride), n_seq, gpl, threads, err, 256)
         if not self.h:
             raise KhhError(err.value.decode())
         self.n_seq, self.stride, self.crypto, self.mode = n_seq, stride, crypto, mode
@@ -520,6 +545,22 @@ class Addr:
         p = lib().khh_addr_table(self.h, C.byref(n))
         raw = C.string_at(p, 20 * n.value) if n.value else b""
         return [raw[20 * i:20 * i + 20] for i in range(n.value)]
+
+    def vanity_intervals(self) -> list[tuple[bytes, bytes]]:
+        """mode="vanity": the merged table [(lo, hi)] of 20-byte big-endian bounds, ascending (khb_load_vanity's)."""
+        n = C.c_uint64(0)
+        p = lib().khh_addr_vanity_intervals(self.h, C.byref(n))
+        raw = C.string_at(p, 40 * n.value) if n.value else b""
+        return [(raw[40 * i:40 * i + 20], raw[40 * i + 20:40 * i + 40]) for i in range(n.value)]
+
+    def vanity_match(self, h20: bytes) -> bytes:
+        """mode="vanity": per 20-byte hash160, bit 0 = inside a merged interval (the device's report), bit 1 = its
+        address begins with a target (the confirmation)."""
+        n = len(h20) // 20
+        out = C.create_string_buffer(n)
+        if lib().khh_addr_vanity_match(self.h, bytes(h20), out, n):
+            raise KhhError("khh_addr_vanity_match: not a vanity handle")
+        return out.raw
 
     def bloom(self) -> tuple[bytes, int, int]:
         nb, bits, h = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
@@ -557,7 +598,8 @@ class Addr:
                random_chunks: bool = False, cap: int = 4096):
         """Found [(key, compressed, rmd160)] in discovery order, plus stats.  search | 4 (KHB_SEARCH_ENDOMORPHISM)
         is -e; search = 8 (KHB_SEARCH_ETH) on a crypto="eth" handle gives (key, False, address); search = 16
-        (KHB_SEARCH_XPOINT), alone or | 4, on a mode="xpoint" handle gives (key, False, first 20 bytes of x)."""
+        (KHB_SEARCH_XPOINT), alone or | 4, on a mode="xpoint" handle gives (key, False, first 20 bytes of x); search
+        0/1/2, optionally | 4, on a mode="vanity" handle gives every key whose address begins with a target."""
         keys = C.create_string_buffer(32 * cap)
         comp = C.create_string_buffer(cap)
         rmd = C.create_string_buffer(20 * cap)
@@ -571,8 +613,8 @@ class Addr:
         if rc:
             raise KhhError(f"khh_addr_search: {err.value.decode()} [{rc}]")
         n = min(nf.value, cap)
-        found = [(int.from_bytes(keys.raw[32 * i:32 * i + 32], "big"), bool(comp.raw[i]), rmd.raw[20 * i:20 * i + 20])
-                 for i in range(n)]
+        kb, cb, rb = keys.raw, comp.raw, rmd.raw     # one copy each: .raw copies the whole buffer
+        found = [(int.from_bytes(kb[32 * i:32 * i + 32], "big"), bool(cb[i]), rb[20 * i:20 * i + 20]) for i in range(n)]
         return found, {"chunks": st[0], "keys": st[1], "hits": st[2], "degenerate": st[3], "kernel_s": st[4] / 1e6,
                        "launches": st[5], "shader_mhz": st[6] / 1e3, "rescans": st[7]}
 
