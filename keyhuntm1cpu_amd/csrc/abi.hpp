@@ -1,6 +1,7 @@
 // Host side of libkhbsgs.so shared by the translation units behind include/khbsgs.h: the context and its
 // submission slots, error mapping, an owned device buffer and the helpers more than one unit uses.
-//   khbsgs.hip        contexts, slots, the scan ABI (submit / collect / scan of both kinds)
+//   khbsgs.hip        contexts, slots, the scan ABI (submit / collect / scan of both kinds; `search` to a kernel mode
+//                     by device/scan_modes.hpp) and launch_scan, the one way to a k_giant_scan launch for every unit
 //   khb_tables.hip    table loads, gate stages, baby and resident builds, the resident inspection calls
 //   khb_selftest.hip  field / probe / hash160 self-tests and the point dumps
 //   k_check.hip       the second / third check: its kernel, tables and khb_check

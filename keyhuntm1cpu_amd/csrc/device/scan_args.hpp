@@ -1,8 +1,9 @@
-// k_giant_scan's vocabulary: kernel modes and predicates, constants, AffPt, ScanArgs, the result-ring writers.
+// k_giant_scan's vocabulary: the modes (scan_modes.hpp), constants, AffPt, ScanArgs, the result-ring writers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../../include/khbsgs.h"
+#include "scan_modes.hpp"
 #include "fe.hpp"
 #include "fe_asm.hpp"
 #include "bloom_probe.hpp"
@@ -49,54 +50,6 @@ constexpr uint32_t kBatch = KHB_BATCH;
 #endif
 constexpr bool kHalfStream = KHB_HALF_STREAM != 0;
 
-// Kernel modes (template argument of k_giant_scan, scan_batch / scan_group and the walks).
-enum : int {
-  kScan = 0,       // -m bsgs: level-1 bloom probe of every x
-  kDump = 1,       // -m bsgs parity: write every x
-  kAddrU = 2,      // -m address, -l uncompress   (2 + keyhunt SEARCH_UNCOMPRESS, keyhunt.cpp:59-61)
-  kAddrC = 3,      // -m address, -l compress
-  kAddrB = 4,      // -m address, -l both (the reference default, keyhunt.cpp:300)
-  kAddrDump = 5,   // -m address parity: write every x||y
-  kBaby = 6,       // baby-step table build: bloom_add of every x into L1/L2/L3 + bPtable records
-  kScanG = 7,      // -m bsgs with a level-0 gate (walk_gated, entered as walk_group_g_half / walk_group_g)
-  kScanG1 = 8,     // kScanG with the gate's stage-1 fold in front (khb_set_gate_stage1)
-  kScanG2 = 9,     // kScanG1 with the stage-0 filter in front of the fold (khb_set_gate_stage0; k >= 4)
-  kAddrUE = 10,    // kAddrU / kAddrC / kAddrB with -e (KHB_SEARCH_ENDOMORPHISM: beta*x, beta^2*x, negated y;
-  kAddrCE = 11,    //   keyhunt.cpp:2646-2763)
-  kAddrBE = 12,
-  kAddrEth = 13,   // -m address -c eth: Keccak-256 of x || y (keyhunt.cpp:2776-2780; device/keccak.hpp)
-  kAddrX = 14,     // -m xpoint: the first 20 bytes of x probed as they are (keyhunt.cpp:3005-3062; device/xpoint.hpp)
-  kAddrXE = 15,    // kAddrX with -e: x, beta*x and beta^2*x (keyhunt.cpp:3013-3043)
-  kVanU = 16,      // -m vanity: kAddrU / kAddrC / kAddrB with the interval match of device/vanity.hpp in the place of
-  kVanC = 17,      //   the target bloom (KHB_SEARCH_VANITY)
-  kVanB = 18,
-  kVanUE = 19,     // -m vanity -e: kAddrUE / kAddrCE / kAddrBE likewise
-  kVanCE = 20,
-  kVanBE = 21,
-};
-constexpr bool is_gated(int m) { return m == kScanG || m == kScanG1 || m == kScanG2; }
-// filter stages in front of the full gate: 0 (kScanG), 1 (the fold, kScanG1), 2 (filter + fold, kScanG2)
-constexpr int gate_stages(int m) { return m == kScanG2 ? 2 : m == kScanG1 ? 1 : 0; }
-constexpr bool is_scan(int m) { return m == kScan || is_gated(m); }
-constexpr bool is_vanity(int m) { return m >= kVanU && m <= kVanBE; }
-// BTC -e (kAddrXE is is_xpoint)
-constexpr bool is_endo(int m) { return (m >= kAddrUE && m <= kAddrBE) || (m >= kVanUE && m <= kVanBE); }
-constexpr bool is_xpoint(int m) { return m == kAddrX || m == kAddrXE; }
-constexpr bool is_addr(int m) {
-  return (m >= kAddrU && m <= kAddrDump) || is_endo(m) || m == kAddrEth || is_xpoint(m) || is_vanity(m);
-}
-constexpr bool addr_compressed(int m) {
-  return m == kAddrC || m == kAddrB || m == kAddrCE || m == kAddrBE || m == kVanC || m == kVanB || m == kVanCE ||
-         m == kVanBE;
-}
-constexpr bool addr_uncompressed(int m) {
-  return m == kAddrU || m == kAddrB || m == kAddrUE || m == kAddrBE || m == kVanU || m == kVanB || m == kVanUE ||
-         m == kVanBE;
-}
-constexpr bool needs_y(int m) { return addr_uncompressed(m) || m == kAddrDump || m == kAddrEth; }
-constexpr bool is_dump(int m) { return m == kDump || m == kAddrDump || m == kBaby; }
-constexpr bool is_batched(int m) { return is_scan(m) || m == kDump; }   // x only, kBatch groups per item (scan_batch)
-constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and y, group by group (scan_group)
 #ifndef KHB_ADDR_WAVES_PER_SIMD
 #define KHB_ADDR_WAVES_PER_SIMD KHB_WAVES_PER_SIMD   // occupancy target of the -m address hash kernels
 #endif
@@ -118,14 +71,10 @@ constexpr bool is_xy(int m) { return is_addr(m) || m == kBaby; }        // x and
 // uses scratch as its address twin does, within 24 B per lane of it (228 to 412 B against 236 to 432 B)
 #define KHB_VANITY_WAVES_PER_SIMD KHB_ADDR_WAVES_PER_SIMD
 #endif
-constexpr int waves_per_simd(int m) {
-  return m == kAddrEth ? KHB_ADDR_ETH_WAVES_PER_SIMD
-         : is_vanity(m) ? KHB_VANITY_WAVES_PER_SIMD
-         : is_xpoint(m) ? KHB_ADDR_X_WAVES_PER_SIMD
-         : is_endo(m)  ? KHB_ADDR_E_WAVES_PER_SIMD
-         : is_addr(m)  ? KHB_ADDR_WAVES_PER_SIMD
-                       : KHB_WAVES_PER_SIMD;
-}
+// the occupancy target of each mode's Occupancy (scan_modes.hpp), in that enum's order
+constexpr int kOccWaves[kOccCount] = {KHB_WAVES_PER_SIMD,          KHB_ADDR_WAVES_PER_SIMD,   KHB_ADDR_E_WAVES_PER_SIMD,
+                                      KHB_ADDR_ETH_WAVES_PER_SIMD, KHB_ADDR_X_WAVES_PER_SIMD, KHB_VANITY_WAVES_PER_SIMD};
+constexpr int waves_per_simd(int m) { return kOccWaves[traits(m).occ]; }
 constexpr uint32_t kHalf = KHB_GROUP / 2;            // 512
 constexpr uint32_t kCandCap = 1u << 20;
 constexpr uint32_t kAddrHitCap = 1u << 18;

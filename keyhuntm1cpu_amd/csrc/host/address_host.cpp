@@ -15,6 +15,8 @@
 
 namespace khb {
 
+using namespace khbk;   // SearchMode and its decoder (device/scan_modes.hpp)
+
 // ------------------------------------------------------------------------------- hashing
 void sha256(const uint8_t* msg, size_t len, uint8_t out[32]) {
   uint32_t s[8], w[16];
@@ -229,15 +231,13 @@ static bool line_h160(TargetKind kind, const std::string& aux, H160& h) {
 bool AddrTargets::load_text(const std::string& text, int bloom_multiplier, AddrTargets& T, std::string* err,
                             TargetKind kind) {
   T = AddrTargets();
+  T.kind = kind;
   if (kind == kTargetsVanity) {          // no bloom and no table: the intervals of vanity_host.hpp
-    T.vanity = true;
     T.van.load_text(text);
     T.skipped = T.van.skipped;
     T.counted = T.van.accepted.size();
     return true;
   }
-  T.eth = kind == kTargetsEth;
-  T.xpoint = kind == kTargetsXpoint;
   const std::vector<std::string> lines = fgets_lines(text, kind == kTargetsXpoint ? 1000 : 100);
   const size_t min_len = kind == kTargetsBtc ? 21 : 40;
   for (const std::string& l : lines)
@@ -342,66 +342,35 @@ const U256& endo_lambda(int e) {
   return L[e - 1];
 }
 
-// The hash is recomputed from the key (independently of the GPU's): P = (lambda^e * k)*G has x = beta^e * x(k*G)
-// and the same y.  Compressed forms 0/1: the x-only hit belongs to k' or to n - k' (keyhunt.cpp:2811-2822; with -e
-// the reference decides by the parity of y, 2800-2860, which gives the same key).  Uncompressed form 2 is k' itself,
-// form 3 (-e only) the negated point, n - k' (keyhunt.cpp:2876-2920).
+// The value is recomputed from the key (independently of the GPU's): P = (lambda^e * k)*G has x = beta^e * x(k*G)
+// and the same y.  Compressed forms 0/1: the x-only hit belongs to k' or to n - k' (keyhunt.cpp:2811-2822; with -e the
+// reference decides by the parity of y, 2800-2860, which gives the same key).  Uncompressed form 2 is k' itself, form
+// 3 (-e only) the negated point, n - k' (keyhunt.cpp:2876-2920).  -c eth and -m xpoint never negate (address_host.hpp).
 bool confirm_hit(const AddrTargets& T, const U256& key, uint32_t kind, AddrFound* out) {
-  if (kind == KHB_ADDR_KIND_ETH) {
-    // -c eth (keyhunt.cpp:2989-3002): the address of key*G itself; the reported key is the scanned key, never negated
-    U256 k;
-    U256::divmod(key, secp_order(), nullptr, &k);
-    if (!T.eth || k.is_zero()) return false;
-    uint8_t h[20];
-    eth_address_pub(mul_g(k), h);
-    if (!T.searchbinary(h)) return false;
-    out->key = key;
-    out->compressed = false;
-    memcpy(out->rmd.data(), h, 20);
-    return true;
-  }
-  if (kind & KHB_ADDR_KIND_X) {
-    // -m xpoint (keyhunt.cpp:3005-3062): searchbinary of the first 20 bytes of beta^e * x(key*G) = x(lambda^e*key*G);
-    // the reported key is lambda^e * key mod n, the walked key itself without -e, and never negated
-    const uint32_t e = (kind & ~(uint32_t)KHB_ADDR_KIND_X) >> 2;
-    if (!T.xpoint || (kind & 3u) || e > 2) return false;
-    U256 k;
-    U256::divmod(key, secp_order(), nullptr, &k);
-    if (e) k = mulmod(k, endo_lambda((int)e), secp_order());
-    if (k.is_zero()) return false;
-    uint8_t xy[64];
-    pt_to_be(xy, mul_g(k));
-    if (!T.searchbinary(xy)) return false;
-    out->key = e ? k : key;
-    out->compressed = false;
-    memcpy(out->rmd.data(), xy, 20);
-    return true;
-  }
-  if (T.eth || T.xpoint) return false;
-  const uint32_t form = kind & 3u, e = kind >> 2;
-  if (e > 2) return false;
+  const bool eth = kind == KHB_ADDR_KIND_ETH, xpoint = !eth && (kind & KHB_ADDR_KIND_X), btc = !eth && !xpoint;
+  const uint32_t form = kind & 3u, e = eth ? 0 : (kind & ~(uint32_t)KHB_ADDR_KIND_X) >> 2;
+  const bool fits = eth ? T.kind == kTargetsEth : xpoint ? T.kind == kTargetsXpoint
+                                                         : T.kind == kTargetsBtc || T.kind == kTargetsVanity;
+  if (!fits || e > 2 || (xpoint && form)) return false;
   U256 k;
   U256::divmod(key, secp_order(), nullptr, &k);
   if (e) k = mulmod(k, endo_lambda((int)e), secp_order());
   if (k.is_zero()) return false;
   const Pt P = mul_g(k);
-  uint8_t h[20];
-  if (form < 2) {
-    hash160_x((uint8_t)(2 + form), P, h);
-    if (!T.is_target(h)) return false;
-    uint8_t hc[20];
+  uint8_t h[64], hc[20];
+  if (eth) eth_address_pub(P, h);
+  else if (xpoint) pt_to_be(h, P);
+  else if (form < 2) hash160_x((uint8_t)(2 + form), P, h);
+  else hash160_pub(form == 2 ? P : negation(P), false, h);
+  if (!T.is_target(h)) return false;
+  bool negated = btc && form == 3;
+  if (btc && form < 2) {
     hash160_pub(P, true, hc);
-    out->key = memcmp(h, hc, 20) != 0 ? secp_order() - k : k;
-    out->compressed = true;
-  } else {
-    hash160_pub(form == 2 ? P : negation(P), false, h);
-    if (!T.is_target(h)) return false;
-    out->key = form == 2 ? k : secp_order() - k;
-    out->compressed = false;
+    negated = memcmp(h, hc, 20) != 0;
   }
   // without -e the reported key is the scanned key itself (key, not key mod n), as the reference's keyfound
-  if (!e && form == 2) out->key = key;
-  else if (!e && form < 2 && out->key == k) out->key = key;
+  out->key = negated ? secp_order() - k : e ? k : key;
+  out->compressed = btc && form < 2;
   memcpy(out->rmd.data(), h, 20);
   return true;
 }
@@ -413,6 +382,7 @@ struct AddrShared {
   const AddrGen& G;
   const AddrConfig& cfg;
   const AddrCallbacks& cb;
+  const SearchMode sm;                 // cfg.search decoded, with the targets' vanity flag
   U256 cursor;
   uint64_t claimed = 0;
   std::mutex mu;
@@ -489,9 +459,7 @@ struct AddrOps {
   }
   int submit(const ABatch& b) {
     const int rc = khb_addr_submit(ctx, b.centres.data(), (uint32_t)b.bases.size(), b.group_begin,
-                                   b.group_count ? b.group_count : groups,
-                                   S.cfg.search | (S.cfg.endomorphism ? KHB_SEARCH_ENDOMORPHISM : 0) |
-                                       (S.T.vanity ? KHB_SEARCH_VANITY : 0));
+                                   b.group_count ? b.group_count : groups, encode_search(S.sm));
     return rc ? fail(rc, "khb_addr_submit") : 0;
   }
   int collect() {
@@ -548,7 +516,7 @@ void device_loop(AddrShared& S, int device) {
   int rc = khb_open(device, S.cfg.lanes, &ctx);
   if (rc) { ops.fail(rc, "khb_open"); return; }
   const std::vector<uint8_t> gtab = S.G.table_be(), offs = S.G.offs_be();
-  const bool vanity = S.T.vanity;
+  const bool vanity = S.sm.vanity;
   const BloomGeom bg = vanity ? BloomGeom{} : S.T.bloom.geom();
   const std::vector<uint8_t> iv = S.T.van.merged_bytes();   // lo || hi per interval
   std::vector<uint8_t> van_lo(iv.size() / 2), van_hi(iv.size() / 2);
@@ -583,7 +551,7 @@ void device_loop(AddrShared& S, int device) {
       // and is rescanned in parts like any other overflow
       // hashes per key: 1 uncompressed, 2 compressed (02 and 03), 3 for both; with -e 6, 6 and 12
       const int hashes[2][3] = {{1, 2, 3}, {6, 6, 12}};
-      const double forms = hashes[S.cfg.endomorphism ? 1 : 0][S.cfg.search];
+      const double forms = hashes[S.sm.endo ? 1 : 0][S.sm.forms];
       const double per_chunk = (double)S.cfg.n_seq * forms * S.T.van.covered();
       const double fit = per_chunk > 0 ? 0.25 * ops.acap / per_chunk : (double)ops.per_batch;
       ops.per_batch = fit < 1 ? 1 : std::min<uint64_t>(ops.per_batch, (uint64_t)fit);
@@ -604,28 +572,31 @@ int addr_search(const AddrTargets& T, const AddrGen& G, const AddrConfig& cfg, c
     if (err) *err = "n must be a positive multiple of 1024";
     return -100;
   }
-  if (T.vanity && (cfg.search < 0 || cfg.search > 2 || T.van.merged.empty())) {
+  SearchMode sm;
+  const bool ok = decode_search(cfg.search, sm) && !sm.vanity;   // the search sets KHB_SEARCH_VANITY, not the caller
+  sm.vanity = T.kind == kTargetsVanity;
+  if (sm.vanity && (!ok || sm.family != kFamilyBtc || T.van.merged.empty())) {
     if (err)
       *err = T.van.merged.empty() ? "there are no vanity targets"
                                   : "vanity targets are searched with search 0, 1 or 2 (-l), optionally with -e";
     return KHB_EINVAL;
   }
-  const bool eth = cfg.search == KHB_SEARCH_ETH, xpoint = cfg.search == KHB_SEARCH_XPOINT;
-  if (eth != T.eth || xpoint != T.xpoint || (eth && cfg.endomorphism) ||
-      (!eth && !xpoint && (cfg.search < 0 || cfg.search > 2))) {
+  const bool eth = sm.family == kFamilyEth, xpoint = sm.family == kFamilyXpoint;
+  if (!ok || (sm.vanity ? kTargetsVanity : eth ? kTargetsEth : xpoint ? kTargetsXpoint : kTargetsBtc) != T.kind) {
     if (err)
-      *err = T.eth      ? "targets loaded for -c eth are searched with KHB_SEARCH_ETH alone (no -l bits, no -e)"
-             : T.xpoint ? "targets loaded for -m xpoint are searched with KHB_SEARCH_XPOINT, optionally with -e (no -l bits)"
-             : eth      ? "KHB_SEARCH_ETH needs targets loaded for -c eth (these are BTC hash160 targets)"
-             : xpoint   ? "KHB_SEARCH_XPOINT needs targets loaded for -m xpoint (these are BTC hash160 targets)"
-                        : "search must be 0, 1 or 2 (-l), optionally with -e";
+      *err = T.kind == kTargetsEth ? "targets loaded for -c eth are searched with KHB_SEARCH_ETH alone (no -l bits, no -e)"
+             : T.kind == kTargetsXpoint
+                 ? "targets loaded for -m xpoint are searched with KHB_SEARCH_XPOINT, optionally with -e (no -l bits)"
+             : eth    ? "KHB_SEARCH_ETH needs targets loaded for -c eth (these are BTC hash160 targets)"
+             : xpoint ? "KHB_SEARCH_XPOINT needs targets loaded for -m xpoint (these are BTC hash160 targets)"
+                      : "search must be 0, 1 or 2 (-l), optionally with -e";
     return KHB_EINVAL;
   }
   if ((cfg.n_seq / 1024 + G.gpl - 1) / G.gpl > G.offs.size()) {
     if (err) *err = "generator lane offsets do not cover a chunk";
     return -100;
   }
-  AddrShared S{T, G, cfg, cb, cfg.start, 0, {}, st, {}, 0};
+  AddrShared S{T, G, cfg, cb, sm, cfg.start, 0, {}, st, {}, 0};
   std::vector<std::thread> th;
   for (int d : cfg.devices) th.emplace_back(device_loop, std::ref(S), d);
   for (auto& t : th) t.join();

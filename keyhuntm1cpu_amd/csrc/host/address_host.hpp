@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../device/scan_modes.hpp"
 #include "bloom_host.hpp"
 #include "secp_host.hpp"
 #include "u256.hpp"
@@ -47,9 +48,8 @@ struct AddrTargets {
   BloomFilter bloom;                   // initBloomFilter(counted lines)
   uint64_t counted = 0;                // lines long enough to count (sizes the bloom)
   std::vector<std::string> skipped;    // "[I] Ommiting invalid line": the trimmed lines
-  bool eth = false;                    // -c eth: the table holds ETH addresses (kTargetsEth)
-  bool xpoint = false;                 // -m xpoint: the table holds the first 20 bytes of x (kTargetsXpoint)
-  bool vanity = false;                 // -m vanity: `van` holds the targets; table and bloom stay empty (kTargetsVanity)
+  TargetKind kind = kTargetsBtc;       // what the table holds: hash160s, ETH addresses or the first 20 bytes of x;
+                                       // kTargetsVanity: `van` holds the targets, table and bloom stay empty
   VanityTargets van;
 
   // text: the target file's contents.  Returns false with *err on an unusable bloom.  counted = lines of more than 20
@@ -67,7 +67,7 @@ struct AddrTargets {
                         TargetKind kind = kTargetsBtc);
   bool searchbinary(const uint8_t h[20]) const;   // keyhunt.cpp:2311-2335, literal
   // h is wanted: searchbinary, or for -m vanity the address of h begins with a target (VanityTargets::matches)
-  bool is_target(const uint8_t h[20]) const { return vanity ? van.matches(h) : searchbinary(h); }
+  bool is_target(const uint8_t h[20]) const { return kind == kTargetsVanity ? van.matches(h) : searchbinary(h); }
 };
 
 struct AddrGen {
@@ -81,11 +81,10 @@ struct AddrGen {
 };
 
 struct AddrConfig {
-  int search = 2;                      // 0 uncompress, 1 compress, 2 both (-l; keyhunt.cpp:59-61, 300),
-                                       // KHB_SEARCH_ETH (-c eth; the targets must be kTargetsEth's) or
-                                       // KHB_SEARCH_XPOINT (-m xpoint; the targets must be kTargetsXpoint's).
-                                       // kTargetsVanity targets take 0, 1 or 2; the search adds KHB_SEARCH_VANITY
-  bool endomorphism = false;           // -e (keyhunt.cpp:579-585): beta*x, beta^2*x and (BTC) negated points
+  int search = 2;                      // khb_addr_submit's `search` (encode_search) without KHB_SEARCH_VANITY, which
+                                       // the search adds for kTargetsVanity targets: -l 0, 1 or 2 (keyhunt.cpp:59-61,
+                                       // 300), KHB_SEARCH_ETH or _XPOINT for targets of that kind, and
+                                       // KHB_SEARCH_ENDOMORPHISM for -e (keyhunt.cpp:579-585)
   U256 start{1}, end{1};               // [start, end): n_range_start / n_range_end
   uint64_t n_seq = 1ull << 32;         // keys per claimed chunk (-n, N_SEQUENTIAL_MAX)
   bool random = false;                 // -R: each chunk starts at a random key in [start, end)

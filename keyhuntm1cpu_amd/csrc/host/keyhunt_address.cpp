@@ -15,6 +15,8 @@
 
 namespace khb {
 
+using namespace khbk;   // SearchMode (device/scan_modes.hpp)
+
 namespace {
 
 // writekey (keyhunt.cpp:5989-6030).  xpoint: f.rmd holds the matched bytes of x, not a hash160, and the reference's
@@ -120,8 +122,8 @@ int run_address_mode(const AddressCli& o) {
   G.build(stride, (uint32_t)(n_seq / 1024), gpl, o.threads > 0 ? o.threads : 1);
   AddrConfig cfg;
   // -c eth: one hash per point whatever -l says; -m xpoint: -l is accepted and not used
-  cfg.search = xpoint ? KHB_SEARCH_XPOINT : o.eth ? KHB_SEARCH_ETH : o.search;
-  cfg.endomorphism = o.endomorphism;
+  cfg.search = encode_search({xpoint ? kFamilyXpoint : o.eth ? kFamilyEth : kFamilyBtc, xpoint || o.eth ? 0 : o.search,
+                              o.endomorphism, false});
   cfg.start = start;
   cfg.end = end;
   cfg.n_seq = n_seq;

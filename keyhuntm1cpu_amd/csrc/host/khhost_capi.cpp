@@ -12,6 +12,7 @@
 #include "engine.hpp"
 
 using namespace khb;
+using namespace khbk;   // SearchMode and its decoder (device/scan_modes.hpp)
 
 struct khh_tables {
   Tables t;
@@ -445,7 +446,7 @@ const uint8_t* khh_addr_vanity_intervals(const khh_addr* a, uint64_t* n) {
 }
 
 int khh_addr_vanity_match(const khh_addr* a, const uint8_t* h20, uint8_t* out, uint64_t n) {
-  if (!a || !a->T.vanity || !h20 || !out) return KHB_EINVAL;
+  if (!a || a->T.kind != kTargetsVanity || !h20 || !out) return KHB_EINVAL;
   for (uint64_t i = 0; i < n; ++i) {
     const uint8_t* h = h20 + 20 * i;
     out[i] = (uint8_t)((a->T.van.in_table(h) ? 1 : 0) | (a->T.van.matches(h) ? 2 : 0));
@@ -502,17 +503,17 @@ int khh_addr_search_ex(const khh_addr* a, const uint8_t start_be[32], const uint
                        int random_chunks, const int* devices, int n_devices, uint32_t lanes, uint64_t max_chunks,
                        uint8_t* keys_be, uint8_t* compressed, uint8_t* rmd, uint32_t cap, uint32_t* n_found,
                        uint64_t* stats_out, uint32_t stats_len, char* err, size_t errlen) {
-  const bool endo = search >= 0 && (search & KHB_SEARCH_ENDOMORPHISM);
-  if (endo) search &= ~KHB_SEARCH_ENDOMORPHISM;
   if (!a || !start_be || !end_be) return KHB_EINVAL;
-  if (search != KHB_SEARCH_ETH && search != KHB_SEARCH_XPOINT && (search < 0 || search > 2)) {
+  // KHB_SEARCH_ETH with -e is no search either, but addr_search answers it with the text about the handle's targets;
+  // KHB_SEARCH_VANITY is the search's to add, not the caller's
+  SearchMode sm;
+  if ((!decode_search(search, sm) && search != (KHB_SEARCH_ETH | KHB_SEARCH_ENDOMORPHISM)) || sm.vanity) {
     set_err(err, errlen, "search must be 0, 1 or 2 (-l) or KHB_SEARCH_XPOINT, optionally with KHB_SEARCH_ENDOMORPHISM, "
                          "or KHB_SEARCH_ETH alone");
     return KHB_EINVAL;
   }
   AddrConfig cfg;
   cfg.search = search;
-  cfg.endomorphism = endo;
   cfg.start = U256::from_be(start_be);
   cfg.end = U256::from_be(end_be);
   cfg.n_seq = a->n_seq;

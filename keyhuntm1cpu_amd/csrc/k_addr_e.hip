@@ -3,15 +3,4 @@
 // `make -j` compiles them beside the plain address kernels (k_addr.hip).
 #include "scan_kernels.hpp"
 
-namespace khbk {
-
-void launch_addr_e(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
-  switch (mode) {
-    case kAddrUE: hipLaunchKernelGGL(k_giant_scan<kAddrUE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kAddrCE: hipLaunchKernelGGL(k_giant_scan<kAddrCE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kAddrBE: hipLaunchKernelGGL(k_giant_scan<kAddrBE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    default: break;
-  }
-}
-
-}  // namespace khbk
+namespace khbk { static const ScanInstances<kAddrBE, kAddrCE, kAddrUE> instances; }

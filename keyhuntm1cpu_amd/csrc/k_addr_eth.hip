@@ -2,10 +2,4 @@
 // in a translation unit of its own beside the BTC address kernels (k_addr.hip, k_addr_e.hip).
 #include "scan_kernels.hpp"
 
-namespace khbk {
-
-void launch_addr_eth(uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
-  hipLaunchKernelGGL(k_giant_scan<kAddrEth>, dim3(blocks), dim3(kBlock), 0, stream, A);
-}
-
-}  // namespace khbk
+namespace khbk { static const ScanInstances<kAddrEth> instances; }

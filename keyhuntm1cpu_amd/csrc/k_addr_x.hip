@@ -3,14 +3,4 @@
 // the address kernels (k_addr.hip, k_addr_e.hip, k_addr_eth.hip).
 #include "scan_kernels.hpp"
 
-namespace khbk {
-
-void launch_addr_x(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
-  switch (mode) {
-    case kAddrX: hipLaunchKernelGGL(k_giant_scan<kAddrX>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kAddrXE: hipLaunchKernelGGL(k_giant_scan<kAddrXE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    default: break;
-  }
-}
-
-}  // namespace khbk
+namespace khbk { static const ScanInstances<kAddrXE, kAddrX> instances; }

@@ -3,18 +3,4 @@
 // their own beside the address kernels (k_addr.hip, k_addr_e.hip).
 #include "scan_kernels.hpp"
 
-namespace khbk {
-
-void launch_vanity(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
-  switch (mode) {
-    case kVanU: hipLaunchKernelGGL(k_giant_scan<kVanU>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kVanC: hipLaunchKernelGGL(k_giant_scan<kVanC>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kVanB: hipLaunchKernelGGL(k_giant_scan<kVanB>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kVanUE: hipLaunchKernelGGL(k_giant_scan<kVanUE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kVanCE: hipLaunchKernelGGL(k_giant_scan<kVanCE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    case kVanBE: hipLaunchKernelGGL(k_giant_scan<kVanBE>, dim3(blocks), dim3(kBlock), 0, stream, A); break;
-    default: break;
-  }
-}
-
-}  // namespace khbk
+namespace khbk { static const ScanInstances<kVanBE, kVanCE, kVanUE, kVanB, kVanC, kVanU> instances; }

@@ -113,11 +113,7 @@ int dump_points(khb_ctx* c, int kind, const uint8_t* centre, uint32_t group_begi
   A.xdump = d;
   uint32_t blocks = (uint32_t)((A.n_items + kBlock - 1) / kBlock);
   if (blocks > c->lanes / kBlock) blocks = c->lanes / kBlock;
-  if (bsgs)
-    launch_bsgs(kDump, blocks, S.stream, A);
-  else
-    launch_addr(kAddrDump, blocks, S.stream, A);
-  if ((rc = sync_launch(c, S.stream))) return rc;
+  if ((rc = launch_scan(bsgs ? kDump : kAddrDump, blocks, S.stream, A)) || (rc = sync_launch(c, S.stream))) return rc;
   KHB_TRY(c, hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
   return KHB_OK;
 }

@@ -172,7 +172,7 @@ int run_baby(khb_ctx* c, Slot& S, const ScanArgs& A, float* kernel_ms) {
   S.counters_zero = false;
   KHB_TRY(c, hipMemsetAsync(S.d_counters, 0, kCounterBytes, S.stream));
   KHB_TRY(c, hipEventRecord(S.ev0, S.stream));
-  launch_baby(c->lanes / kBlock, S.stream, A);
+  if (const int rc = launch_scan(kBaby, c->lanes / kBlock, S.stream, A)) return rc;
   KHB_TRY(c, hipGetLastError());
   KHB_TRY(c, hipEventRecord(S.ev1, S.stream));
   KHB_TRY(c, hipStreamSynchronize(S.stream));

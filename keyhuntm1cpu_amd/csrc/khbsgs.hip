@@ -258,6 +258,14 @@ int ensure_gofs(khb_ctx* c) {
   return KHB_OK;
 }
 
+ScanLauncher g_scan_launchers[kModeCount];   // filled by the units' ScanInstances while the library loads
+
+int launch_scan(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
+  if (mode < 0 || mode >= kModeCount || !g_scan_launchers[mode]) return KHB_EINVAL;
+  g_scan_launchers[mode](blocks, stream, A);
+  return KHB_OK;
+}
+
 }  // namespace khbk
 
 namespace {
@@ -270,20 +278,9 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
   const bool bsgs = kind == 1;
   int rc = check_scan_args(c, centres, n_jobs, group_begin, group_count, bsgs);
   if (rc) return rc;
-  // -m vanity: the BTC kernels (-l bits, optionally -e) over the interval table; with -c eth or -m xpoint it is
-  // KHB_EINVAL (khbsgs.h)
-  const bool vanity = !bsgs && search >= 0 && (search & KHB_SEARCH_VANITY);
-  if (vanity) {
-    search &= ~KHB_SEARCH_VANITY;
-    if (search & (KHB_SEARCH_ETH | KHB_SEARCH_XPOINT)) return KHB_EINVAL;
-  }
-  const bool eth = !bsgs && search == KHB_SEARCH_ETH;     // exactly: no -l bits, no -e (khbsgs.h)
-  // -m xpoint: alone or with -e; with -l bits or -c eth it is KHB_EINVAL (khbsgs.h)
-  const bool xpoint = !bsgs && search >= 0 && (search & ~KHB_SEARCH_ENDOMORPHISM) == KHB_SEARCH_XPOINT;
-  const bool endo = !bsgs && !eth && search >= 0 && (search & KHB_SEARCH_ENDOMORPHISM);
-  if (endo) search &= ~KHB_SEARCH_ENDOMORPHISM;
-  if (!bsgs && !eth && !xpoint && (search < 0 || search > 2)) return KHB_EINVAL;
-  if (!(bsgs ? (void*)c->d_bloom : vanity ? (void*)c->d_van : (void*)c->d_abloom)) return KHB_ESTATE;
+  SearchMode sm;
+  if (!bsgs && !decode_search(search, sm)) return KHB_EINVAL;
+  if (!(bsgs ? (void*)c->d_bloom : sm.vanity ? (void*)c->d_van : (void*)c->d_abloom)) return KHB_ESTATE;
   if (c->queued && c->slot[c->head].kind != kind) return KHB_EBUSY;     // a scan of the other kind is in flight
   KHB_TRY(c, hipSetDevice(c->device));
   Slot* Sp = next_slot(c, rc);
@@ -303,7 +300,7 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
     A.geom = c->ageom;
     A.ahits = S.h_ahits;
     A.ahit_cap = khb_addr_hit_capacity(c);
-    if (vanity) {
+    if (sm.vanity) {
       A.van_lo = c->d_van;
       A.van_hi = c->d_van + 5 * (size_t)c->van_n;
       A.van_bitmap = c->d_van + 10 * (size_t)c->van_n;
@@ -314,19 +311,8 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
   const uint32_t blocks = c->lanes / kBlock;
   if ((rc = prepare_host_launch(c, S, A, blocks))) return rc;
   KHB_TRY(c, hipEventRecord(S.ev0, S.stream));
-  if (bsgs)
-    launch_bsgs(c->d_gate0 ? kScanG2 : c->d_gate1 ? kScanG1 : c->d_gate ? kScanG : kScan, blocks, S.stream, A);
-  else if (eth)
-    launch_addr_eth(blocks, S.stream, A);
-  else if (xpoint)
-    launch_addr_x(endo ? kAddrXE : kAddrX, blocks, S.stream, A);
-  else if (vanity)
-    launch_vanity(endo ? (search == 0 ? kVanUE : search == 1 ? kVanCE : kVanBE)
-                       : (search == 0 ? kVanU : search == 1 ? kVanC : kVanB), blocks, S.stream, A);
-  else if (endo)
-    launch_addr_e(search == 0 ? kAddrUE : search == 1 ? kAddrCE : kAddrBE, blocks, S.stream, A);
-  else
-    launch_addr(search == 0 ? kAddrU : search == 1 ? kAddrC : kAddrB, blocks, S.stream, A);
+  const int mode = bsgs ? (c->d_gate0 ? kScanG2 : c->d_gate1 ? kScanG1 : c->d_gate ? kScanG : kScan) : scan_mode_of(sm);
+  if ((rc = launch_scan(mode, blocks, S.stream, A))) return rc;
   KHB_TRY(c, hipGetLastError());
   KHB_TRY(c, hipEventRecord(S.ev1, S.stream));
   S.total_waves = A.total_waves;

@@ -1,7 +1,7 @@
 // Device side of libkhbsgs (gfx950): the giant-step walk and its kernel k_giant_scan<MODE>, shared by
 // the translation units that instantiate it (k_bsgs.hip: -m bsgs scan / x dump; k_addr*.hip: -m address, -m xpoint;
-// k_baby.hip: baby-step tables) and by khbsgs.hip (types, self-test kernels, the C ABI).  Splitting the
-// instances over translation units lets `make -j` compile them in parallel.
+// k_vanity.hip: -m vanity; k_baby.hip: baby-step tables) and by khbsgs.hip (launch_scan, the C ABI).  Splitting the
+// instances over units lets `make -j` compile them in parallel; device/scan_modes.hpp says what each mode is.
 //
 // Hot path replaced: keyhunt.cpp:3867-4004 (thread_process_bsgs group loop + level-1 bloom probe).
 //
@@ -120,13 +120,22 @@ __global__ __launch_bounds__(kBlock, waves_per_simd(MODE)) void k_giant_scan(Sca
   launch_epilogue(A);
 }
 
-// Launchers of the k_giant_scan instances (one translation unit each, see above).
-void launch_bsgs(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);   // kScan, kScanG, kScanG1, kScanG2, kDump
-void launch_addr(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);   // kAddrU, kAddrC, kAddrB, kAddrDump
-void launch_addr_e(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrUE, kAddrCE, kAddrBE
-void launch_addr_eth(uint32_t blocks, hipStream_t stream, const ScanArgs& A);         // kAddrEth
-void launch_addr_x(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kAddrX, kAddrXE
-void launch_vanity(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);  // kVanU ... kVanBE
-void launch_baby(uint32_t blocks, hipStream_t stream, const ScanArgs& A);             // kBaby
+// The launch of every instance.  A unit states its instances once, as a ScanInstances<...> object, and launch_scan
+// (khbsgs.hip) finds them by mode: KHB_EINVAL for a mode no unit instantiates.  The compiler emits a unit's kernels in
+// the reverse of its list, so the lists run from the last instance to the first: the code objects' layout of before.
+using ScanLauncher = void (*)(uint32_t blocks, hipStream_t stream, const ScanArgs& A);
+extern ScanLauncher g_scan_launchers[kModeCount];
+
+template <int MODE>
+void launch_instance(uint32_t blocks, hipStream_t stream, const ScanArgs& A) {
+  hipLaunchKernelGGL(k_giant_scan<MODE>, dim3(blocks), dim3(kBlock), 0, stream, A);
+}
+
+template <int... MODES>
+struct ScanInstances {
+  ScanInstances() { ((g_scan_launchers[MODES] = &launch_instance<MODES>), ...); }
+};
+
+int launch_scan(int mode, uint32_t blocks, hipStream_t stream, const ScanArgs& A);
 
 }  // namespace khbk

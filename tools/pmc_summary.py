@@ -42,7 +42,7 @@ sys.path.insert(0, REPO)
 GROUPS = 4096          # k=1 default geometry: groups per chunk (cycles)
 GROUPS_BY_K = {1: 4096, 4: 1024}   # cycles per chunk of the default -n 2^44 geometry
 CUS, SIMDS = 256, 4
-GATED_MODES = (7, 8, 9)   # device/scan_args.hpp kScanG, kScanG1, kScanG2
+GATED_MODES = (7, 8, 9)   # device/scan_modes.hpp kScanG, kScanG1, kScanG2
 
 
 def dispatches(d, meta=False):
