@@ -13,11 +13,19 @@
 // read by the scalar unit on the common path (s_or_b64 / s_cmp: interlocked, no pad) and, in the
 // wave-uniform carry fix only, by v_cndmask as its select mask: a VALU read of a VALU-written SGPR,
 // which fm_fix_R pads with `s_nop 1` on top of the whole R chain that already lies between the two.
+// The same holds for every other rare carry (fm_mask_bit below): R9 out of the R chain, the two carries of
+// the one-mad second fold, fm_add_lazy's carry and fm_sub's borrow into limb 2 are written to SGPR pairs
+// by the VOP3 form of the instruction that produces them (its carry-in still VCC, behind KHB_NOP), read on
+// the common path by s_or_b64 / s_cmp only, and by a VALU (v_cndmask, behind `s_nop 1`) only inside the
+// wave-uniform rare branch.  The second fold is in its pair form (fm_reduce_V): m = 977 R8 + (R1:R0) as
+// one mad on an even-aligned register pair that the chain leaves in place; the form without a pair (a mad
+// with addend 0 and two more adds) was not needed, the pair costs no copy (profiles/r09_fold2/hot_path.txt).
 //
 // Value contract (checked by tests/test_gpu_scan.py::test_field_ops and every x-dump test):
 //   * fm_mul / fm_sqr return a value < 2^256 congruent to a*b mod p, not necessarily < p ("lazy").
 //     The lazy value is a function of the operands alone: the same for every lane whether or not its
-//     wave took a rare branch or the reduction's carry fix (tests/test_gpu_field_reduce.py, raw mode).
+//     wave took a rare branch or the reduction's carry fix (tests/test_gpu_field_reduce.py and
+//     tests/test_gpu_field_fold2.py, raw mode).
 //   * fm_sub(a, b) is correct for a < 2^256 and b < p; its result is < 2^256 (< p if it borrowed).
 //   * fm_add(a, b) needs a, b < p and returns a canonical value.
 //   * fm_canon brings any value < 2^256 into [0, p).  Values that are hashed, compared or used as a
@@ -41,9 +49,25 @@ namespace khb {
 #define KHB_NOP "s_nop 0\n\t"
 #if KHB_RARE_FORCE    // test builds: always take the rare branch (its full propagation is a no-op at c = 0)
 FM_DEV bool fm_any(uint32_t) { return true; }
+FM_DEV bool fm_any_mask(uint64_t) { return true; }
 #else
 FM_DEV bool fm_any(uint32_t c) { return __builtin_expect(__ballot(c != 0) != 0, 0); }
+FM_DEV bool fm_any_mask(uint64_t m) { return __builtin_expect(m != 0, 0); }
 #endif
+// The rare carry as a lane mask: the instruction that produces the carry (VOP3 form of v_addc / v_subb /
+// v_mad_u64_u32) writes it to an SGPR pair instead of VCC, fm_any_mask tests the pair on the scalar unit
+// (interlocked, no pad), and only the rare branch turns it into a per-lane 0/1 with fm_mask_bit.  Against
+// "v_addc c, vcc, 0, 0, vcc" + a v_cmp for the ballot that is two half-rate VALU instructions less per
+// call.  The hardware writes 0 to the mask bits of lanes that are inactive at the write, so a lane that
+// sits out cannot raise the branch; and if a bit were stale it could only send the wave through a branch
+// body that leaves that lane alone (it is still inactive there) and adds 0 in every other lane.
+// fm_mask_bit is a VALU read of a VALU-written SGPR: `s_nop 1` ahead of it, as in fm_fix_R.
+FM_DEV uint32_t fm_mask_bit(uint64_t m) {
+  uint32_t c;
+  asm("s_nop 1\n\t"
+      "v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(c) : "s"(m));
+  return c;
+}
 
 // r[k..7] += c (c in {0, 1} per lane), carry-out returned.
 template <int K>
@@ -267,49 +291,53 @@ FM_DEV void fm_sqr512x(uint32_t t[16], const uint32_t* a) {
 // words 2..9; a no-op for lanes that did not carry).  After it R is S as 10 words, which is the
 // representation the T = Lw + (H << 32), P_i = 977 H_i + T_i form of this reduction produced, so
 // the second fold and the value returned (lazy, < 2^256) are bit for bit what they were.
-#if KHB_RARE_FORCE
-FM_DEV bool fm_any_mask(uint64_t) { return true; }
-#else
-FM_DEV bool fm_any_mask(uint64_t m) { return __builtin_expect(m != 0, 0); }
-#endif
+// The second fold takes the same route (below): R9, the top word of R, and the two carries out of the
+// folded limbs are lane masks in SGPR pairs, tested together with the ov masks; the common path has
+// no R9 register and folds R8 alone.
 
-// V = 977*h + (h : lw); ov = lane mask of the carry-out.  977 comes from an SGPR (VOP3 takes no
-// literal on gfx9; one scalar source per instruction is the constant-bus limit).
-FM_DEV void fm_madv(uint64_t& V, uint64_t& ov, uint32_t h, uint32_t lw, uint32_t k977) {
-  const uint64_t hl = ((uint64_t)h << 32) | lw;
-  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(V), "=s"(ov) : "v"(h), "s"(k977), "v"(hl));
+// d = a*k + c (c a 64-bit register pair); co = lane mask of the carry-out.  k comes from an SGPR (VOP3
+// takes no literal on gfx9; one scalar source per instruction is the constant-bus limit).
+FM_DEV void fm_mad_co(uint64_t& d, uint64_t& co, uint32_t a, uint32_t k, uint64_t c) {
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(co) : "v"(a), "s"(k), "v"(c));
 }
 
-// R9:R8:R[7..0] = sum_i V_i 2^(32i) + T8 2^256 : one carry chain.
-FM_DEV void fm_chain_R(uint32_t R[8], uint32_t& R8, uint32_t& R9, const uint64_t V[8], uint32_t T8) {
+// V = 977*h + (h : lw); ov = lane mask of the carry-out.
+FM_DEV void fm_madv(uint64_t& V, uint64_t& ov, uint32_t h, uint32_t lw, uint32_t k977) {
+  fm_mad_co(V, ov, h, k977, ((uint64_t)h << 32) | lw);
+}
+
+// R8:R[7..0] = sum_i V_i 2^(32i) + T8 2^256 (mod 2^288): one carry chain.  The carry out of R8 -- R9, the
+// tenth word -- is not materialised: the add that produces R8 writes it to the lane mask m9 (VOP3 form).
+// R[1] overwrites the high word of V_0, so that R[1]:R[0] stays the register pair the second fold's mad
+// takes as its addend.
+FM_DEV void fm_chain_R(uint32_t R[8], uint32_t& R8, uint64_t& m9, const uint64_t V[8], uint32_t T8) {
   R[0] = (uint32_t)V[0];
-  asm("v_add_co_u32_e32 %0, vcc, %9, %10\n\t"
+  R[1] = (uint32_t)(V[0] >> 32);
+  asm("v_add_co_u32_e32 %0, vcc, %9, %0\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %11, %12, vcc\n\t"
+      "v_addc_co_u32_e32 %1, vcc, %10, %11, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %13, %14, vcc\n\t"
+      "v_addc_co_u32_e32 %2, vcc, %12, %13, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %15, %16, vcc\n\t"
+      "v_addc_co_u32_e32 %3, vcc, %14, %15, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %17, %18, vcc\n\t"
+      "v_addc_co_u32_e32 %4, vcc, %16, %17, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %19, %20, vcc\n\t"
+      "v_addc_co_u32_e32 %5, vcc, %18, %19, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %21, %22, vcc\n\t"
+      "v_addc_co_u32_e32 %6, vcc, %20, %21, vcc\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %23, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
-      : "=&v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]),
-        "=&v"(R8), "=&v"(R9)
-      : "v"((uint32_t)V[1]), "v"((uint32_t)(V[0] >> 32)),
+      "v_addc_co_u32_e64 %7, %8, %22, %23, vcc"
+      : "+v"(R[1]), "=&v"(R[2]), "=&v"(R[3]), "=&v"(R[4]), "=&v"(R[5]), "=&v"(R[6]), "=&v"(R[7]),
+        "=&v"(R8), "=s"(m9)
+      : "v"((uint32_t)V[1]),
         "v"((uint32_t)V[2]), "v"((uint32_t)(V[1] >> 32)),
         "v"((uint32_t)V[3]), "v"((uint32_t)(V[2] >> 32)),
         "v"((uint32_t)V[4]), "v"((uint32_t)(V[3] >> 32)),
         "v"((uint32_t)V[5]), "v"((uint32_t)(V[4] >> 32)),
         "v"((uint32_t)V[6]), "v"((uint32_t)(V[5] >> 32)),
         "v"((uint32_t)V[7]), "v"((uint32_t)(V[6] >> 32)),
-        "v"(T8), "v"((uint32_t)(V[7] >> 32)), "v"(0u)
+        "v"(T8), "v"((uint32_t)(V[7] >> 32))
       : "vcc");
 }
 
@@ -349,15 +377,10 @@ FM_DEV void fm_fix_R(uint32_t R[8], uint32_t& R8, uint32_t& R9, const uint64_t o
       : "vcc");
 }
 
-// Lw + Lw8 2^256 + H (2^32 + 977) -> a value < 2^256 congruent to it (lazy).
-FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t* H) {
-  uint64_t V[8], ov[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) fm_madv(V[i], ov[i], H[i], Lw[i], 977u);
-  uint32_t R[8], R8, R9;              // top = R9:R8 < 3 * 2^32 once the carries are in
-  fm_chain_R(R, R8, R9, V, Lw8);
-  if (fm_any_mask(ov[0] | ov[1] | ov[2] | ov[3] | ov[4] | ov[5] | ov[6] | ov[7])) fm_fix_R(R, R8, R9, ov);
-  // second fold: top = R9:R8 (< 3 * 2^32); add top*977 at limb 0 and top*2^32 at limb 1
+// The second fold in its general form: R[7..0] += top (2^32 + 977) for top = R9:R8 < 3 * 2^32, carries
+// and the wrap past 2^256 included.  Only reached through fm_reduce_V's rare branch.
+FM_DEV void fm_fold2(uint32_t R[8], uint32_t R8, uint32_t R9) {
+  // add top*977 at limb 0 and top*2^32 at limb 1
   const uint64_t u = (uint64_t)R8 * 977u + (uint64_t)(R9 * 977u) * 0x100000000ull;   // < 2^44
   const uint64_t w = (uint64_t)(uint32_t)(u >> 32) + R8;                              // limb-1 addend
   const uint32_t w2 = (uint32_t)(w >> 32) + R9;                                       // limb-2 addend (<= 3)
@@ -384,8 +407,49 @@ FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t*
     R[1] = (uint32_t)t;
     fm_propagate<2>(R, (uint32_t)(t >> 32));
   }
+}
+
+// Lw + Lw8 2^256 + H (2^32 + 977) -> a value < 2^256 congruent to it (lazy).
+FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t* H) {
+  uint64_t V[8], ov[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) r.v[i] = R[i];
+  for (int i = 0; i < 8; ++i) fm_madv(V[i], ov[i], H[i], Lw[i], 977u);
+  uint32_t R[8], R8;
+  uint64_t m9;                        // lane mask of R9 (0/1 before the carry fix)
+  fm_chain_R(R, R8, m9, V, Lw8);
+  // Second fold, common form (R9 = 0, no V carry): R + R8 (2^32 + 977) over limbs 0..2 is
+  //   m = R8*977 + (R1:R0)   one mad on the register pair, carry-out o (R1:R0 >= 2^64 - 977 R8: ~2^-22)
+  //   R0' = lo(m), R1' = hi(m) + R8, R2' = R2 + carry, with the carry out of R2' in the mask c2m
+  // written to registers of their own.  It is the general fold's value unless o is set (the mad dropped
+  // 2^64); c2m is the general fold's c3.  One wave-uniform branch on every mask then redoes the fold in
+  // its general form from the untouched R0, R1, R2, R8, for all lanes of the wave: a lane the common
+  // form was right for gets the same three words again.  (Two branches, one for ov | m9 ahead of the
+  // common form and one for o | c2m behind it, would hold the general fold twice per reduction and
+  // test twice; the three instructions saved in a wave that is rare anyway are not worth that.)
+  const uint64_t r01 = ((uint64_t)R[1] << 32) | R[0];
+  uint64_t m, o, c2m;
+  uint32_t n1, n2;
+  fm_mad_co(m, o, R8, 977u, r01);
+  n1 = (uint32_t)(m >> 32);           // R1' takes the place of hi(m): R1':R0' stays a pair, no copy
+  asm("v_add_co_u32_e32 %0, vcc, %3, %0\n\t"
+      KHB_NOP
+      "v_addc_co_u32_e64 %1, %2, 0, %4, vcc"
+      : "+v"(n1), "=&v"(n2), "=s"(c2m)
+      : "v"(R8), "v"(R[2])
+      : "vcc");
+  const uint64_t anyov = ov[0] | ov[1] | ov[2] | ov[3] | ov[4] | ov[5] | ov[6] | ov[7];
+  r.v[0] = (uint32_t)m;
+  r.v[1] = n1;
+  r.v[2] = n2;
+#pragma unroll
+  for (int i = 3; i < 8; ++i) r.v[i] = R[i];
+  if (fm_any_mask(anyov | m9 | o | c2m)) {
+    uint32_t R9 = fm_mask_bit(m9);    // top = R9:R8 < 3 * 2^32 once the carries are in
+    if (fm_any_mask(anyov)) fm_fix_R(R, R8, R9, ov);
+    fm_fold2(R, R8, R9);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = R[i];
+  }
 }
 
 // Reduce t (512 bits) mod p to a value < 2^256 (lazy).
@@ -447,7 +511,8 @@ FM_DEV void fm_sqr_add(Fe& r, const Fe& a, const Fe& w) {
 
 // a - b mod p for a < 2^256, b < p.
 FM_DEV void fm_sub(Fe& r, const Fe& a, const Fe& b) {
-  uint32_t d[8], m, k0, k1, b2;
+  uint32_t d[8], m, k0, k1;
+  uint64_t b2;           // lane mask: the correction borrowed out of limb 1 (fm_mask_bit's comment)
   asm("v_sub_co_u32_e32 %0, vcc, %12, %20\n\t"
       KHB_NOP
       "v_subb_co_u32_e32 %1, vcc, %13, %21, vcc\n\t"
@@ -470,18 +535,16 @@ FM_DEV void fm_sub(Fe& r, const Fe& a, const Fe& b) {
       "v_and_b32_e32 %10, 1, %8\n\t"
       "v_sub_co_u32_e32 %0, vcc, %0, %9\n\t"
       KHB_NOP
-      "v_subb_co_u32_e32 %1, vcc, %1, %10, vcc\n\t"
-      KHB_NOP
-      // the borrow into limb 2 (probability ~2^-32) is propagated in the rare branch
-      "v_subb_co_u32_e32 %11, vcc, 0, %28, vcc"
+      // the borrow into limb 2 (probability ~2^-32) goes to the mask and is propagated in the rare branch
+      "v_subb_co_u32_e64 %1, %11, %1, %10, vcc"
       : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7]),
-        "=&v"(m), "=&v"(k0), "=&v"(k1), "=&v"(b2)
+        "=&v"(m), "=&v"(k0), "=&v"(k1), "=s"(b2)
       : "v"(a.v[0]), "v"(a.v[1]), "v"(a.v[2]), "v"(a.v[3]), "v"(a.v[4]), "v"(a.v[5]), "v"(a.v[6]), "v"(a.v[7]),
         "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7]),
         "v"(0u)
       : "vcc");
-  if (fm_any(b2)) {      // b2 = 0xffffffff where the correction borrowed out of limb 1
-    uint32_t bo = b2 & 1u;
+  if (fm_any_mask(b2)) {
+    uint32_t bo = fm_mask_bit(b2);
 #pragma unroll
     for (int i = 2; i < 8; ++i) {
       const uint32_t t = d[i] - bo;
@@ -556,19 +619,18 @@ FM_DEV void fm_add_lazy(Fe& r, const Fe& a, const Fe& b) {
         "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7]),
         "v"(0u)
       : "vcc");
-  // fold the carry as 2^256 = 0x1000003D1: limbs 0..1 always; the carry into limb 2 only behind
-  // the rare branch
-  uint32_t c2;
-  asm("v_mul_u32_u24_e32 %2, 0x3d1, %3\n\t"
+  // fold the carry as 2^256 = 0x1000003D1: limbs 0..1 always; the carry into limb 2 goes to a lane
+  // mask (fm_mask_bit's comment) and is propagated only behind the rare branch
+  uint32_t k;
+  uint64_t c2;
+  asm("v_mul_u32_u24_e32 %2, 0x3d1, %4\n\t"
       "v_add_co_u32_e32 %0, vcc, %0, %2\n\t"
       KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %1, %3, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, 0, %4, vcc"
-      : "+v"(s[0]), "+v"(s[1]), "=&v"(c2)
-      : "v"(c), "v"(0u)
+      "v_addc_co_u32_e64 %1, %3, %1, %4, vcc"
+      : "+v"(s[0]), "+v"(s[1]), "=&v"(k), "=s"(c2)
+      : "v"(c)
       : "vcc");
-  if (fm_any(c2)) fm_propagate<2>(s, c2);
+  if (fm_any_mask(c2)) fm_propagate<2>(s, fm_mask_bit(c2));
 #pragma unroll
   for (int i = 0; i < 8; ++i) r.v[i] = s[i];
 }

@@ -11,7 +11,8 @@ Inputs (all under profiles/):
   r05c/f64mul_time.jsonl   the field product's energy (fm_mul chains alone at full occupancy)
   r06b/prof/pmc_latest.json  VALU lane-instructions per giant step of the round-6 kernel, the one every input above
                            was measured on (profiles/pmc_latest.json follows the current kernel: 680.4 since the
-                           per-limb reduction, whose power and class counts have not been re-taken)
+                           per-limb reduction, 635.5 since the one-mad second fold, whose power and class counts have
+                           not been re-taken)
 Prints one JSON object; tests/test_measure_tools.py checks it against the figures DESIGN.md quotes.
 Usage: python tools/energy_split.py"""
 import collections
