@@ -92,12 +92,25 @@ FM_DEV void fm_madc(uint64_t& acc, uint32_t& c2, uint32_t a, uint32_t b) {
       : "vcc");
 }
 
-// ---- 512-bit products without accumulator shuffling ----------------------------------------
-// Column k (sum of a_i*b_{k-i}) accumulates in its own 64-bit pair A[k]; the carries out of A[k]
-// (weight 2^(32k+64)) are counted in cw[k] and seed A[k+2], which they align with exactly.  So no
-// register is ever moved between columns; one add chain at the end folds hi(A[k-1]) into word k:
-//   sum_k A[k] 2^(32k) (+ cw[13] 2^480) == a*b.
-// The first product of a column cannot overflow (seed < 2^4), the others carry into cw[k].
+// ---- 512-bit products with forward-carried columns -------------------------------------------
+// Column K (sum of a_i*b_{K-i}) accumulates in one 64-bit pair S whose two halves weigh 2^(32K) and
+// 2^(32K+32); the carries out of S (weight 2^(32K+64)) are counted in cw.  The next column's pair starts as
+//   {lo = hi(S), hi = cw}
+// which is exactly what column K hands on: both words weigh in column K+1 what the halves of its own pair
+// weigh.  So the column's first mad adds the carried word for nothing, t[K] = lo(S) with no fold chain
+// behind the columns, and two pairs are live at a time instead of fifteen.  Column 14 (one product, or
+// none in the squaring's cross sum) leaves t[14], t[15] as its two halves: the whole product is < 2^512.
+//
+// The first product of a column is a mad without a carry count.  A product is at most (2^32 - 1)^2 =
+// 2^64 - 2^33 + 1, so that is exact while the seed is <= 2^33 - 2: always when the column before holds one
+// or two products (then what it hands on, floor(total / 2^32), stays below that), not always when it holds
+// three or more (cw >= 2, or cw = 1 under a full high word): columns 3..13 of a product, 6..10 of the cross
+// sum.  It takes a first product within 2^35 of 2^64 (~2^-29 per column for random limbs; certain for
+// all-ones operands).  Those columns' first mad writes its carry-out to an SGPR pair of its own (VOP3 always
+// names a scalar destination: no instruction more), the masks are ORed on the scalar unit, and a
+// wave-uniform branch adds the dropped carries back: the one out of column K weighs 2^(32(K+2)), and since
+// everything after the drop was computed exactly from the smaller count, t falls short of the product by
+// exactly those bits (fm_fix_cols, one chain; a no-op for lanes that dropped nothing).
 
 // acc += a*b; cw = carry-out (first carry of a column: no zero-initialisation needed)
 FM_DEV void fm_madc_first(uint64_t& acc, uint32_t& cw, uint32_t a, uint32_t b) {
@@ -109,119 +122,130 @@ FM_DEV void fm_madc_first(uint64_t& acc, uint32_t& cw, uint32_t a, uint32_t b) {
       : "vcc");
 }
 
+// acc += a*b; co = lane mask of the carry-out (a column's first product on a seed that can reach 2^33 - 1)
+FM_DEV void fm_mad_seed(uint64_t& acc, uint64_t& co, uint32_t a, uint32_t b) {
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(acc), "=s"(co) : "v"(a), "v"(b));
+}
+
+// The products of a column after its first: cw receives their carries.
+template <int LO, int HI, int K>
+FM_DEV void fm_col_rest(uint64_t& A, uint32_t& cw, const uint32_t* a, const uint32_t* b) {
+  if constexpr (HI > LO) {
+    fm_madc_first(A, cw, a[LO + 1], b[K - LO - 1]);
+#pragma unroll
+    for (int i = LO + 2; i <= HI; ++i) fm_madc(A, cw, a[i], b[K - i]);
+  }
+}
+
 // Column K of a*b (generic product): A seeded, cw receives its carries.
 template <int K>
 FM_DEV void fm_colx(uint64_t& A, uint32_t& cw, const uint32_t* a, const uint32_t* b) {
   constexpr int lo = K > 7 ? K - 7 : 0, hi = K < 7 ? K : 7;
   A += (uint64_t)a[lo] * b[K - lo];
-  if constexpr (hi > lo) {
-    fm_madc_first(A, cw, a[lo + 1], b[K - lo - 1]);
+  fm_col_rest<lo, hi, K>(A, cw, a, b);
+}
+
+// The same with the first product's carry-out in the lane mask co.
+template <int K>
+FM_DEV void fm_colx(uint64_t& A, uint32_t& cw, uint64_t& co, const uint32_t* a, const uint32_t* b) {
+  constexpr int lo = K > 7 ? K - 7 : 0, hi = K < 7 ? K : 7;
+  fm_mad_seed(A, co, a[lo], b[K - lo]);
+  fm_col_rest<lo, hi, K>(A, cw, a, b);
+}
+
+// The pair column K+1 starts from: the high word of column K's pair and its carry count.
+FM_DEV uint64_t fm_col_next(uint64_t S, uint32_t cw) { return ((uint64_t)cw << 32) | (uint32_t)(S >> 32); }
+
+// w[0..W-1] += sum_i bit_i 2^(32i), bit_i the lane's bit of mask m[i] (i < N): w[0] is the word two above
+// the first masked column.  Nothing leaves w[W-1]: with the bits in, the words are those of the product.
+template <int N, int W>
+FM_DEV void fm_fix_cols(uint32_t* w, const uint64_t* m) {
+  uint32_t c = 0;
 #pragma unroll
-    for (int i = lo + 2; i <= hi; ++i) fm_madc(A, cw, a[i], b[K - i]);
+  for (int i = 0; i < W; ++i) {
+    uint64_t s = (uint64_t)w[i] + c;
+    if (i < N) s += fm_mask_bit(m[i]);
+    w[i] = (uint32_t)s;
+    c = (uint32_t)(s >> 32);
   }
 }
 
-// t[k] = lo(A[k]) + hi(A[k-1]) + carry, k = 1..14; t[15] = cw13 + hi(A[14]) + carry.
-FM_DEV void fm_fold_cols(uint32_t t[16], const uint64_t A[15], uint32_t cw13) {
-#define FM_LO(k) "v"((uint32_t)A[k])
-#define FM_HI(k) "v"((uint32_t)(A[k] >> 32))
-  t[0] = (uint32_t)A[0];
-  asm("v_add_co_u32_e32 %0, vcc, %15, %16\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %17, %18, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %19, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %21, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %23, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %25, %26, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %27, %28, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %29, %30, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, %31, %32, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %9, vcc, %33, %34, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %10, vcc, %35, %36, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %11, vcc, %37, %38, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %12, vcc, %39, %40, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %13, vcc, %41, %42, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %14, vcc, %43, %44, vcc"
-      : "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
-        "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11]), "=&v"(t[12]), "=&v"(t[13]), "=&v"(t[14]),
-        "=&v"(t[15])
-      : FM_LO(1), FM_HI(0), FM_LO(2), FM_HI(1), FM_LO(3), FM_HI(2), FM_LO(4), FM_HI(3), FM_LO(5), FM_HI(4),
-        FM_LO(6), FM_HI(5), FM_LO(7), FM_HI(6), FM_LO(8), FM_HI(7), FM_LO(9), FM_HI(8), FM_LO(10), FM_HI(9),
-        FM_LO(11), FM_HI(10), FM_LO(12), FM_HI(11), FM_LO(13), FM_HI(12), FM_LO(14), FM_HI(13), "v"(cw13),
-        FM_HI(14)
-      : "vcc");
-#undef FM_LO
-#undef FM_HI
-}
-
 FM_DEV void fm_mul512x(uint32_t t[16], const uint32_t* a, const uint32_t* b) {
-  uint64_t A[15];
-  uint32_t cw[14];
-  A[0] = (uint64_t)a[0] * b[0];
-  A[1] = 0;
-  fm_colx<1>(A[1], cw[1], a, b);
-  A[2] = 0;
-  fm_colx<2>(A[2], cw[2], a, b);
-#define FM_COLX(K)            \
-  A[K] = (uint64_t)cw[K - 2]; \
-  fm_colx<K>(A[K], cw[K], a, b);
+  uint64_t S = (uint64_t)a[0] * b[0];
+  uint64_t m[11];                     // first-product carry-outs of columns 3..13
+  uint32_t cw;
+  t[0] = (uint32_t)S;
+  S >>= 32;                           // column 0 is one product: nothing to count
+  fm_colx<1>(S, cw, a, b);
+  t[1] = (uint32_t)S;
+  S = fm_col_next(S, cw);
+  fm_colx<2>(S, cw, a, b);
+  t[2] = (uint32_t)S;
+#define FM_COLX(K)                      \
+  S = fm_col_next(S, cw);               \
+  fm_colx<K>(S, cw, m[K - 3], a, b);    \
+  t[K] = (uint32_t)S;
   FM_COLX(3) FM_COLX(4) FM_COLX(5) FM_COLX(6) FM_COLX(7) FM_COLX(8) FM_COLX(9) FM_COLX(10)
   FM_COLX(11) FM_COLX(12) FM_COLX(13)
 #undef FM_COLX
-  A[14] = (uint64_t)cw[12];
-  A[14] += (uint64_t)a[7] * b[7];
-  fm_fold_cols(t, A, cw[13]);
+  S = fm_col_next(S, cw);
+  S += (uint64_t)a[7] * b[7];
+  t[14] = (uint32_t)S;
+  t[15] = (uint32_t)(S >> 32);
+  if (fm_any_mask(m[0] | m[1] | m[2] | m[3] | m[4] | m[5] | m[6] | m[7] | m[8] | m[9] | m[10]))
+    fm_fix_cols<11, 11>(t + 5, m);
 }
 
-// Column K of the cross sum sum_{i<j} a_i a_j 2^(32(i+j)).
+// Column K of the cross sum sum_{i<j} a_i a_j 2^(32(i+j)); the second form as fm_colx's.
 template <int K>
 FM_DEV void fm_colsq(uint64_t& A, uint32_t& cw, const uint32_t* a) {
   constexpr int lo = K > 7 ? K - 7 : 0, hi = (K - 1) / 2;   // pairs (i, K-i), i < K-i
   A += (uint64_t)a[lo] * a[K - lo];
-  if constexpr (hi > lo) {
-    fm_madc_first(A, cw, a[lo + 1], a[K - lo - 1]);
-#pragma unroll
-    for (int i = lo + 2; i <= hi; ++i) fm_madc(A, cw, a[i], a[K - i]);
-  }
+  fm_col_rest<lo, hi, K>(A, cw, a, a);
+}
+
+template <int K>
+FM_DEV void fm_colsq(uint64_t& A, uint32_t& cw, uint64_t& co, const uint32_t* a) {
+  constexpr int lo = K > 7 ? K - 7 : 0, hi = (K - 1) / 2;
+  fm_mad_seed(A, co, a[lo], a[K - lo]);
+  fm_col_rest<lo, hi, K>(A, cw, a, a);
 }
 
 // a^2 = 2*cross + diag: 36 products instead of 64.
 FM_DEV void fm_sqr512x(uint32_t t[16], const uint32_t* a) {
-  uint64_t A[15];
-  uint32_t cw[14];
-  A[0] = 0;
-  A[1] = 0;
-  fm_colsq<1>(A[1], cw[1], a);
-  A[2] = 0;
-  fm_colsq<2>(A[2], cw[2], a);
-  A[3] = 0;
-  fm_colsq<3>(A[3], cw[3], a);
-  A[4] = 0;
-  fm_colsq<4>(A[4], cw[4], a);
-#define FM_COLSQ(K)           \
-  A[K] = (uint64_t)cw[K - 2]; \
-  fm_colsq<K>(A[K], cw[K], a);
-  FM_COLSQ(5) FM_COLSQ(6) FM_COLSQ(7) FM_COLSQ(8) FM_COLSQ(9) FM_COLSQ(10) FM_COLSQ(11) FM_COLSQ(12)
-  FM_COLSQ(13)
-#undef FM_COLSQ
-  A[14] = 0;                  // column 14 holds no cross product (7,7 is diagonal)
-  // Only columns 3..11 hold two or more cross products, so only cw[3..11] exist; they seed
-  // A[5..13].  Columns 1, 2, 12, 13 carry nothing.
+  // Cross sum c, columns carried forward as in fm_mul512x.  Only columns 3..11 hold two or more cross
+  // products and count carries; columns 1, 2, 12, 13 hold one and column 14 none (7,7 is diagonal), so c[14]
+  // is column 13's high word and c[15] = 0: the cross sum is < 2^481, with the dropped carries back in too.
   uint32_t c[16];
-  fm_fold_cols(c, A, 0u);     // c = cross sum (c[0] = 0)
+  uint64_t S = (uint64_t)a[0] * a[1];
+  uint64_t m[5];                      // first-product carry-outs of columns 6..10
+  uint32_t cw;
+  c[0] = 0u;
+  c[1] = (uint32_t)S;
+  S >>= 32;
+  fm_colsq<2>(S, cw, a);
+  c[2] = (uint32_t)S;
+  S >>= 32;
+  fm_colsq<3>(S, cw, a);
+  c[3] = (uint32_t)S;
+#define FM_COLSQ(K)         \
+  S = fm_col_next(S, cw);   \
+  fm_colsq<K>(S, cw, a);    \
+  c[K] = (uint32_t)S;
+#define FM_COLSQM(K)                  \
+  S = fm_col_next(S, cw);             \
+  fm_colsq<K>(S, cw, m[K - 6], a);    \
+  c[K] = (uint32_t)S;
+  FM_COLSQ(4) FM_COLSQ(5) FM_COLSQM(6) FM_COLSQM(7) FM_COLSQM(8) FM_COLSQM(9) FM_COLSQM(10) FM_COLSQ(11)
+  FM_COLSQ(12)
+#undef FM_COLSQ
+#undef FM_COLSQM
+  S >>= 32;                           // column 12 is one product: cw is not written
+  fm_colsq<13>(S, cw, a);
+  c[13] = (uint32_t)S;
+  c[14] = (uint32_t)(S >> 32);
+  c[15] = 0u;
+  if (fm_any_mask(m[0] | m[1] | m[2] | m[3] | m[4])) fm_fix_cols<5, 7>(c + 8, m);
   uint64_t D[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) D[i] = (uint64_t)a[i] * a[i];
@@ -488,7 +512,7 @@ FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
   fm_reduce_V(r, U, U[8], t + 8);
 }
 
-// Multiply / square: seeded columns (fm_mul512x / fm_sqr512x), then the reduction.  (The column-shuffle
+// Multiply / square: forward-carried columns (fm_mul512x / fm_sqr512x), then the reduction.  (The column-shuffle
 // and fold-as-completed schedules were measured slower: profiles/r01_fmbench.txt.)
 FM_DEV void fm_mul(Fe& r, const Fe& a, const Fe& b) {
   uint32_t t[16];
