@@ -1,38 +1,43 @@
-// gfx950 fast path for the secp256k1 field: hand-placed carry chains.
+// gfx950 fast path for the secp256k1 field: 8 x 32-bit limbs, hand-placed carry chains.
 //
 // Why: the scan kernel is VALU-issue-bound (profiles/r01_pmc.txt).  The portable fe.hpp compiles
 // to 390 VALU instructions per multiply — 216 of them v_mov_b32 materialising zero-extended
 // 64-bit addends.  Here each 32x32 partial product is one v_mad_u64_u32 whose carry-out (VCC)
 // is absorbed by one VOP2 v_addc_co_u32 (product scanning), and add/sub are single carry chains.
-//
-// gfx950 hazard: a VALU that writes VCC (v_add_co/v_sub_co/v_mad_u64_u32 carry-out) needs one
-// wait state before a VALU reads that VCC as carry-in — hipcc pads its own chains with `s_nop 0`
-// (seen in its ISA for __builtin_addc), but nothing inside an asm string is padded
-// (cdna_hip_programming.md §5.7 item 2), so every carry consumer below is preceded by `s_nop 0`.
-// The reduction's V mads (fm_madv) write their carry-out to SGPR pairs instead of VCC.  Those masks are
-// read by the scalar unit on the common path (s_or_b64 / s_cmp: interlocked, no pad) and, in the
-// wave-uniform carry fix only, by v_cndmask as its select mask: a VALU read of a VALU-written SGPR,
-// which fm_fix_R pads with `s_nop 1` on top of the whole R chain that already lies between the two.
-// The same holds for every other rare carry (fm_mask_bit below): R9 out of the R chain, the two carries of
-// the one-mad second fold, fm_add_lazy's carry and fm_sub's borrow into limb 2 are written to SGPR pairs
-// by the VOP3 form of the instruction that produces them (its carry-in still VCC, behind KHB_NOP), read on
-// the common path by s_or_b64 / s_cmp only, and by a VALU (v_cndmask, behind `s_nop 1`) only inside the
-// wave-uniform rare branch.  The second fold is in its pair form (fm_reduce_V): m = 977 R8 + (R1:R0) as
-// one mad on an even-aligned register pair that the chain leaves in place; the form without a pair (a mad
-// with addend 0 and two more adds) was not needed, the pair costs no copy (profiles/r09_fold2/hot_path.txt).
+// How the file came to this form, and what was tried and left out: DESIGN.md §2a (field arithmetic), §5.
 //
 // Value contract (checked by tests/test_gpu_scan.py::test_field_ops and every x-dump test):
-//   * fm_mul / fm_sqr return a value < 2^256 congruent to a*b mod p, not necessarily < p ("lazy").
-//     The lazy value is a function of the operands alone: the same for every lane whether or not its
-//     wave took a rare branch or the reduction's carry fix (tests/test_gpu_field_reduce.py and
-//     tests/test_gpu_field_fold2.py, raw mode).
+//   * fm_mul / fm_sqr / fm_sqr_add return a value < 2^256 congruent to the result mod p, not necessarily
+//     < p ("lazy").  The lazy value is a function of the operands alone: the same for every lane whether
+//     or not its wave took a rare branch (tests/field_model.py defines it on integers;
+//     tests/test_gpu_field_directed.py compares it in raw mode).
+//   * fm_add_lazy(a, b) takes a < p, b < 2^256 and returns a lazy value.
 //   * fm_sub(a, b) is correct for a < 2^256 and b < p; its result is < 2^256 (< p if it borrowed).
 //   * fm_add(a, b) needs a, b < p and returns a canonical value.
 //   * fm_canon brings any value < 2^256 into [0, p).  Values that are hashed, compared or used as a
 //     subtrahend (x-coordinates, centres) are canonicalised, so every observable equals the
 //     reference's canonical Int (IntMod.cpp) bit for bit.
+//
+// Hazard rules.  hipcc pads its own carry chains (seen in its ISA for __builtin_addc) but nothing inside
+// an asm string (cdna_hip_programming.md §5.7 item 2), so the pads are written out:
+//   * KHB_NOP (`s_nop 0`): a VALU that writes VCC (v_add_co / v_sub_co / v_mad_u64_u32 carry-out) needs one
+//     wait state before a VALU reads that VCC as carry-in.  Every carry consumer is preceded by it.
+//   * `s_nop 1` ahead of a VALU read (v_cndmask's select mask) of an SGPR pair that a VALU wrote:
+//     fm_mask_bit and fm_fix_R.  Scalar reads of such a pair (s_or_b64, s_cmp) are interlocked: no pad.
+//
+// Rare carries.  A carry or borrow that is set with probability 2^-22 or less per call (each function
+// gives its own figure) is not propagated on the common path.  The instruction that produces it, in its
+// VOP3 form (v_addc / v_subb / v_mad_u64_u32; carry-in still VCC), writes it as a lane mask to an SGPR
+// pair instead of VCC; a function's masks are ORed and tested on the scalar unit (fm_any_mask), and one
+// wave-uniform branch, taken when some lane needs it, turns each mask into a per-lane 0/1 (fm_mask_bit)
+// and does the full propagation: a no-op for lanes whose bit is 0.  Against "v_addc c, vcc, 0, 0, vcc" +
+// a v_cmp for a ballot that is two half-rate VALU instructions less per call.  The hardware writes 0 to
+// the mask bits of lanes that are inactive at the write, so a lane that sits out cannot raise the branch;
+// a stale bit could only send the wave through a body that leaves that lane alone (it is still inactive
+// there) and adds 0 in every other lane.
 #pragma once
 #include <stdint.h>
+#include <utility>
 
 #include "fe.hpp"
 
@@ -40,12 +45,8 @@ namespace khb {
 
 #define FM_DEV __device__ __forceinline__
 
-// Rare carries: carry/borrow propagation past limb 1/2 that happens with probability ~2^-30 per call
-// (the fold of 2^256 = 0x1000003D1 into a random 256-bit value) runs behind a wave-uniform branch
-// taken only when some lane needs it; the common path stops the chain at the limb that produces
-// the carry.  The branch body is the full propagation, a no-op for lanes whose carry is 0.
-// KHB_NOP: the one wait state between a VCC (carry) write and its VALU reader.  (A timing-only build
-// without it was 1.1 % faster, profiles/r01_nonop_ab.txt; the pads stay as the hazard rule asks.)
+// The one wait state between a VCC (carry) write and its VALU reader.  (A timing-only build without it
+// was 1.1 % faster, profiles/r01_nonop_ab.txt; the pads stay as the hazard rule asks.)
 #define KHB_NOP "s_nop 0\n\t"
 #if KHB_RARE_FORCE    // test builds: always take the rare branch (its full propagation is a no-op at c = 0)
 FM_DEV bool fm_any(uint32_t) { return true; }
@@ -54,14 +55,7 @@ FM_DEV bool fm_any_mask(uint64_t) { return true; }
 FM_DEV bool fm_any(uint32_t c) { return __builtin_expect(__ballot(c != 0) != 0, 0); }
 FM_DEV bool fm_any_mask(uint64_t m) { return __builtin_expect(m != 0, 0); }
 #endif
-// The rare carry as a lane mask: the instruction that produces the carry (VOP3 form of v_addc / v_subb /
-// v_mad_u64_u32) writes it to an SGPR pair instead of VCC, fm_any_mask tests the pair on the scalar unit
-// (interlocked, no pad), and only the rare branch turns it into a per-lane 0/1 with fm_mask_bit.  Against
-// "v_addc c, vcc, 0, 0, vcc" + a v_cmp for the ballot that is two half-rate VALU instructions less per
-// call.  The hardware writes 0 to the mask bits of lanes that are inactive at the write, so a lane that
-// sits out cannot raise the branch; and if a bit were stale it could only send the wave through a branch
-// body that leaves that lane alone (it is still inactive there) and adds 0 in every other lane.
-// fm_mask_bit is a VALU read of a VALU-written SGPR: `s_nop 1` ahead of it, as in fm_fix_R.
+// The lane's bit of a carry mask as 0/1; only inside a rare branch.
 FM_DEV uint32_t fm_mask_bit(uint64_t m) {
   uint32_t c;
   asm("s_nop 1\n\t"
@@ -105,12 +99,12 @@ FM_DEV void fm_madc(uint64_t& acc, uint32_t& c2, uint32_t a, uint32_t b) {
 // 2^64 - 2^33 + 1, so that is exact while the seed is <= 2^33 - 2: always when the column before holds one
 // or two products (then what it hands on, floor(total / 2^32), stays below that), not always when it holds
 // three or more (cw >= 2, or cw = 1 under a full high word): columns 3..13 of a product, 6..10 of the cross
-// sum.  It takes a first product within 2^35 of 2^64 (~2^-29 per column for random limbs; certain for
-// all-ones operands).  Those columns' first mad writes its carry-out to an SGPR pair of its own (VOP3 always
-// names a scalar destination: no instruction more), the masks are ORed on the scalar unit, and a
-// wave-uniform branch adds the dropped carries back: the one out of column K weighs 2^(32(K+2)), and since
-// everything after the drop was computed exactly from the smaller count, t falls short of the product by
-// exactly those bits (fm_fix_cols, one chain; a no-op for lanes that dropped nothing).
+// sum (FmCol::masked works the bound out).  It takes a first product within 2^35 of 2^64 (~2^-29 per column
+// for random limbs; certain for all-ones operands).  Those columns' first mad writes its carry-out to an
+// SGPR pair of its own (VOP3 always names a scalar destination: no instruction more) and the rare branch
+// adds the dropped carries back: the one out of column K weighs 2^(32(K+2)), and since everything after
+// the drop was computed exactly from the smaller count, t falls short of the product by exactly those
+// bits (fm_fix_cols, one chain).
 
 // acc += a*b; cw = carry-out (first carry of a column: no zero-initialisation needed)
 FM_DEV void fm_madc_first(uint64_t& acc, uint32_t& cw, uint32_t a, uint32_t b) {
@@ -137,27 +131,57 @@ FM_DEV void fm_col_rest(uint64_t& A, uint32_t& cw, const uint32_t* a, const uint
   }
 }
 
-// Column K of a*b (generic product): A seeded, cw receives its carries.
-template <int K>
-FM_DEV void fm_colx(uint64_t& A, uint32_t& cw, const uint32_t* a, const uint32_t* b) {
-  constexpr int lo = K > 7 ? K - 7 : 0, hi = K < 7 ? K : 7;
-  A += (uint64_t)a[lo] * b[K - lo];
-  fm_col_rest<lo, hi, K>(A, cw, a, b);
-}
-
-// The same with the first product's carry-out in the lane mask co.
-template <int K>
-FM_DEV void fm_colx(uint64_t& A, uint32_t& cw, uint64_t& co, const uint32_t* a, const uint32_t* b) {
-  constexpr int lo = K > 7 ? K - 7 : 0, hi = K < 7 ? K : 7;
-  fm_mad_seed(A, co, a[lo], b[K - lo]);
-  fm_col_rest<lo, hi, K>(A, cw, a, b);
-}
-
 // The pair column K+1 starts from: the high word of column K's pair and its carry count.
 FM_DEV uint64_t fm_col_next(uint64_t S, uint32_t cw) { return ((uint64_t)cw << 32) | (uint32_t)(S >> 32); }
 
+// The shape of column K: the products a_i b_{K-i}, lo <= i <= hi, of a*b, or (SQ) of the cross sum
+// sum_{i<j} a_i a_j 2^(32(i+j)), whose pairs are i < K-i with b = a.
+template <int K, bool SQ>
+struct FmCol {
+  static constexpr int count(int k) {           // products in column k
+    const int l = k > 7 ? k - 7 : 0, h = SQ ? (k - 1) / 2 : (k < 7 ? k : 7);
+    return k < (SQ ? 1 : 0) || h < l ? 0 : h - l + 1;
+  }
+  // The first product can overflow its seed: the most column k-1 hands on, floor(total / 2^32) with every
+  // product at its maximum, plus one such product passes 2^64 (tests/field_columns.py unsafe_columns).
+  static constexpr bool unsafe(int k) {
+    constexpr uint64_t pmax = 0xFFFFFFFE00000001ull;   // (2^32 - 1)^2
+    unsigned __int128 v = 0;
+    for (int j = 0; j < k; ++j) v = (count(j) * (unsigned __int128)pmax + v) >> 32;
+    return count(k) && v + pmax > ~0ull;
+  }
+  static constexpr int first_unsafe(int k) { return unsafe(k) ? k : first_unsafe(k + 1); }
+  static constexpr int lo = K > 7 ? K - 7 : 0, hi = SQ ? (K - 1) / 2 : (K < 7 ? K : 7);
+  static constexpr int n = count(K), first_masked = first_unsafe(0);
+  static constexpr bool masked = unsafe(K);
+};
+static_assert(!FmCol<2, false>::masked && FmCol<3, false>::masked && FmCol<13, false>::masked &&
+              !FmCol<14, false>::masked, "fm_mul512x: m[0..10] are columns 3..13");
+static_assert(!FmCol<5, true>::masked && FmCol<6, true>::masked && FmCol<10, true>::masked &&
+              !FmCol<11, true>::masked, "fm_sqr512x: m[0..4] are columns 6..10");
+
+// Column K on top of column K-1: the seed, the products, t[K].  A column of one product hands on its high
+// word alone (its cw is not written).  m[K - first_masked] receives a masked column's first carry-out.
+template <int K, bool SQ>
+FM_DEV void fm_col(uint32_t* t, uint64_t& S, uint32_t& cw, uint64_t* m, const uint32_t* a, const uint32_t* b) {
+  using C = FmCol<K, SQ>;
+  if constexpr (FmCol<K - 1, SQ>::n >= 2) S = fm_col_next(S, cw); else S >>= 32;
+  if constexpr (C::masked) fm_mad_seed(S, m[K - C::first_masked], a[C::lo], b[K - C::lo]);
+  else S += (uint64_t)a[C::lo] * b[K - C::lo];
+  fm_col_rest<C::lo, C::hi, K>(S, cw, a, b);
+  t[K] = (uint32_t)S;
+}
+
+template <bool SQ, int K0, int... I>   // columns K0 + I, in order
+FM_DEV void fm_cols(uint32_t* t, uint64_t& S, uint32_t& cw, uint64_t* m, const uint32_t* a, const uint32_t* b,
+                    std::integer_sequence<int, I...>) {
+  (fm_col<K0 + I, SQ>(t, S, cw, m, a, b), ...);
+}
+
 // w[0..W-1] += sum_i bit_i 2^(32i), bit_i the lane's bit of mask m[i] (i < N): w[0] is the word two above
 // the first masked column.  Nothing leaves w[W-1]: with the bits in, the words are those of the product.
+// (The reduction's fm_fix_R is the same thing written as one asm chain, and stays that: as
+// fm_fix_cols<8, 8> on a 10-word R it costs k_giant_scan<0, 7, 8, 9> 256 bytes of scratch against 160-168.)
 template <int N, int W>
 FM_DEV void fm_fix_cols(uint32_t* w, const uint64_t* m) {
   uint32_t c = 0;
@@ -175,40 +199,10 @@ FM_DEV void fm_mul512x(uint32_t t[16], const uint32_t* a, const uint32_t* b) {
   uint64_t m[11];                     // first-product carry-outs of columns 3..13
   uint32_t cw;
   t[0] = (uint32_t)S;
-  S >>= 32;                           // column 0 is one product: nothing to count
-  fm_colx<1>(S, cw, a, b);
-  t[1] = (uint32_t)S;
-  S = fm_col_next(S, cw);
-  fm_colx<2>(S, cw, a, b);
-  t[2] = (uint32_t)S;
-#define FM_COLX(K)                      \
-  S = fm_col_next(S, cw);               \
-  fm_colx<K>(S, cw, m[K - 3], a, b);    \
-  t[K] = (uint32_t)S;
-  FM_COLX(3) FM_COLX(4) FM_COLX(5) FM_COLX(6) FM_COLX(7) FM_COLX(8) FM_COLX(9) FM_COLX(10)
-  FM_COLX(11) FM_COLX(12) FM_COLX(13)
-#undef FM_COLX
-  S = fm_col_next(S, cw);
-  S += (uint64_t)a[7] * b[7];
-  t[14] = (uint32_t)S;
+  fm_cols<false, 1>(t, S, cw, m, a, b, std::make_integer_sequence<int, 14>{});   // columns 1..14
   t[15] = (uint32_t)(S >> 32);
   if (fm_any_mask(m[0] | m[1] | m[2] | m[3] | m[4] | m[5] | m[6] | m[7] | m[8] | m[9] | m[10]))
     fm_fix_cols<11, 11>(t + 5, m);
-}
-
-// Column K of the cross sum sum_{i<j} a_i a_j 2^(32(i+j)); the second form as fm_colx's.
-template <int K>
-FM_DEV void fm_colsq(uint64_t& A, uint32_t& cw, const uint32_t* a) {
-  constexpr int lo = K > 7 ? K - 7 : 0, hi = (K - 1) / 2;   // pairs (i, K-i), i < K-i
-  A += (uint64_t)a[lo] * a[K - lo];
-  fm_col_rest<lo, hi, K>(A, cw, a, a);
-}
-
-template <int K>
-FM_DEV void fm_colsq(uint64_t& A, uint32_t& cw, uint64_t& co, const uint32_t* a) {
-  constexpr int lo = K > 7 ? K - 7 : 0, hi = (K - 1) / 2;
-  fm_mad_seed(A, co, a[lo], a[K - lo]);
-  fm_col_rest<lo, hi, K>(A, cw, a, a);
 }
 
 // a^2 = 2*cross + diag: 36 products instead of 64.
@@ -222,27 +216,7 @@ FM_DEV void fm_sqr512x(uint32_t t[16], const uint32_t* a) {
   uint32_t cw;
   c[0] = 0u;
   c[1] = (uint32_t)S;
-  S >>= 32;
-  fm_colsq<2>(S, cw, a);
-  c[2] = (uint32_t)S;
-  S >>= 32;
-  fm_colsq<3>(S, cw, a);
-  c[3] = (uint32_t)S;
-#define FM_COLSQ(K)         \
-  S = fm_col_next(S, cw);   \
-  fm_colsq<K>(S, cw, a);    \
-  c[K] = (uint32_t)S;
-#define FM_COLSQM(K)                  \
-  S = fm_col_next(S, cw);             \
-  fm_colsq<K>(S, cw, m[K - 6], a);    \
-  c[K] = (uint32_t)S;
-  FM_COLSQ(4) FM_COLSQ(5) FM_COLSQM(6) FM_COLSQM(7) FM_COLSQM(8) FM_COLSQM(9) FM_COLSQM(10) FM_COLSQ(11)
-  FM_COLSQ(12)
-#undef FM_COLSQ
-#undef FM_COLSQM
-  S >>= 32;                           // column 12 is one product: cw is not written
-  fm_colsq<13>(S, cw, a);
-  c[13] = (uint32_t)S;
+  fm_cols<true, 2>(c, S, cw, m, a, a, std::make_integer_sequence<int, 12>{});    // columns 2..13
   c[14] = (uint32_t)(S >> 32);
   c[15] = 0u;
   if (fm_any_mask(m[0] | m[1] | m[2] | m[3] | m[4])) fm_fix_cols<5, 7>(c + 8, m);
@@ -307,17 +281,13 @@ FM_DEV void fm_sqr512x(uint32_t t[16], const uint32_t* a) {
 //   V_i = 977 H_i + (H_i : Lw_i)                                     (sum_i V_i 2^(32i) + Lw8 2^256 == S)
 // one v_mad_u64_u32 whose 64-bit addend is the register pair {lo = Lw_i, hi = H_i}: no carry chain
 // for Lw + (H << 32) and no zero-extended addend.  V_i < 2^64 + 977 2^32, so the mad carries out
-// when H_i >= ~2^32 - 978 (2^-22 per limb for random limbs, certain for operands near p).  Each mad
-// writes its carry-out to an SGPR pair of its own (not VCC); the eight lane masks are ORed on the
-// scalar unit.  The chain R = sum_i lo64(V_i) 2^(32i) + Lw8 2^256 then runs on the truncated V_i, and
-// when any lane of the wave carried, a wave-uniform branch adds the dropped carries back: the one
-// out of V_i weighs 2^(32(i+2)), so it is a 0/1 addend of R's word i+2 (fm_fix_R, one chain over
-// words 2..9; a no-op for lanes that did not carry).  After it R is S as 10 words, which is the
-// representation the T = Lw + (H << 32), P_i = 977 H_i + T_i form of this reduction produced, so
-// the second fold and the value returned (lazy, < 2^256) are bit for bit what they were.
-// The second fold takes the same route (below): R9, the top word of R, and the two carries out of the
-// folded limbs are lane masks in SGPR pairs, tested together with the ov masks; the common path has
-// no R9 register and folds R8 alone.
+// when H_i >= ~2^32 - 978 (2^-22 per limb for random limbs, certain for operands near p): each mad has
+// a mask of its own (ov_i).  The chain R = sum_i lo64(V_i) 2^(32i) + Lw8 2^256 runs on the truncated
+// V_i, and the rare branch adds the dropped carries back: the one out of V_i weighs 2^(32(i+2)), a 0/1
+// addend of R's word i+2 (fm_fix_R, one chain over words 2..9).  After it R is S as 10 words.  The second
+// fold adds top (2^32 + 977), top = R9:R8, to R[7..0].  R9 and the two carries out of the folded limbs are
+// masks too, tested together with the ov_i: the common path has no R9 register and folds R8 alone in one
+// mad (fm_reduce_V); the rare branch holds the fold in its general form (fm_fold2).
 
 // d = a*k + c (c a 64-bit register pair); co = lane mask of the carry-out.  k comes from an SGPR (VOP3
 // takes no literal on gfx9; one scalar source per instruction is the constant-bus limit).
@@ -447,9 +417,7 @@ FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t*
   // written to registers of their own.  It is the general fold's value unless o is set (the mad dropped
   // 2^64); c2m is the general fold's c3.  One wave-uniform branch on every mask then redoes the fold in
   // its general form from the untouched R0, R1, R2, R8, for all lanes of the wave: a lane the common
-  // form was right for gets the same three words again.  (Two branches, one for ov | m9 ahead of the
-  // common form and one for o | c2m behind it, would hold the general fold twice per reduction and
-  // test twice; the three instructions saved in a wave that is rare anyway are not worth that.)
+  // form was right for gets the same three words again.
   const uint64_t r01 = ((uint64_t)R[1] << 32) | R[0];
   uint64_t m, o, c2m;
   uint32_t n1, n2;
@@ -479,13 +447,9 @@ FM_DEV void fm_reduce_V(Fe& r, const uint32_t* Lw, uint32_t Lw8, const uint32_t*
 // Reduce t (512 bits) mod p to a value < 2^256 (lazy).
 FM_DEV void fm_reduce(Fe& r, const uint32_t t[16]) { fm_reduce_V(r, t, 0u, t + 8); }
 
-// (t + w) mod p, lazy (< 2^256), for t a 512-bit product and any w < 2^256: the addend rides in
-// one carry chain U = L + w ahead of the V mads, so a following modular add/sub (x = s^2 - u)
-// costs 9 instructions instead of 19.  U + (H << 32) < 2^288 + 2^257, the bound R9:R8 < 3 * 2^32
-// relies on.
-FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
-  const uint32_t* L = t;
-  uint32_t U[9];
+// s = a + b mod 2^256 as one carry chain; the carry out of limb 7 (0/1) is returned.
+FM_DEV uint32_t fm_add8(uint32_t s[8], const uint32_t* a, const uint32_t* b) {
+  uint32_t c;
   asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
       KHB_NOP
       "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
@@ -503,13 +467,23 @@ FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
       "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
       KHB_NOP
       "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
-      : "=&v"(U[0]), "=&v"(U[1]), "=&v"(U[2]), "=&v"(U[3]), "=&v"(U[4]), "=&v"(U[5]), "=&v"(U[6]), "=&v"(U[7]),
-        "=&v"(U[8])
-      : "v"(L[0]), "v"(L[1]), "v"(L[2]), "v"(L[3]), "v"(L[4]), "v"(L[5]), "v"(L[6]), "v"(L[7]),
-        "v"(w.v[0]), "v"(w.v[1]), "v"(w.v[2]), "v"(w.v[3]), "v"(w.v[4]), "v"(w.v[5]), "v"(w.v[6]), "v"(w.v[7]),
+      : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]), "=&v"(s[6]), "=&v"(s[7]),
+        "=&v"(c)
+      : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]),
+        "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]),
         "v"(0u)
       : "vcc");
-  fm_reduce_V(r, U, U[8], t + 8);
+  return c;
+}
+
+// (t + w) mod p, lazy (< 2^256), for t a 512-bit product and any w < 2^256: the addend rides in
+// one carry chain U = L + w ahead of the V mads, so a following modular add/sub (x = s^2 - u)
+// costs 9 instructions instead of 19.  U + (H << 32) < 2^288 + 2^257, the bound R9:R8 < 3 * 2^32
+// relies on.
+FM_DEV void fm_reduce_add(Fe& r, const uint32_t t[16], const Fe& w) {
+  uint32_t U[8];
+  const uint32_t U8 = fm_add8(U, t, w.v);
+  fm_reduce_V(r, U, U8, t + 8);
 }
 
 // Multiply / square: forward-carried columns (fm_mul512x / fm_sqr512x), then the reduction.  (The column-shuffle
@@ -536,7 +510,7 @@ FM_DEV void fm_sqr_add(Fe& r, const Fe& a, const Fe& w) {
 // a - b mod p for a < 2^256, b < p.
 FM_DEV void fm_sub(Fe& r, const Fe& a, const Fe& b) {
   uint32_t d[8], m, k0, k1;
-  uint64_t b2;           // lane mask: the correction borrowed out of limb 1 (fm_mask_bit's comment)
+  uint64_t b2;           // lane mask: the correction borrowed out of limb 1 (head comment, rare carries)
   asm("v_sub_co_u32_e32 %0, vcc, %12, %20\n\t"
       KHB_NOP
       "v_subb_co_u32_e32 %1, vcc, %13, %21, vcc\n\t"
@@ -619,32 +593,10 @@ FM_DEV void fm_canon(Fe& r, const Fe& a) {
 // a + b mod p, lazy: for a < p and b < 2^256 (so a + b < 2^257 - 0x1000003D1) the sum folds its
 // carry back as 2^256 = 0x1000003D1 (mod p) and stays < 2^256.  Feeds a product only.
 FM_DEV void fm_add_lazy(Fe& r, const Fe& a, const Fe& b) {
-  uint32_t s[8], c;
-  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"       // c = carry (0/1)
-      : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]), "=&v"(s[6]), "=&v"(s[7]),
-        "=&v"(c)
-      : "v"(a.v[0]), "v"(a.v[1]), "v"(a.v[2]), "v"(a.v[3]), "v"(a.v[4]), "v"(a.v[5]), "v"(a.v[6]), "v"(a.v[7]),
-        "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7]),
-        "v"(0u)
-      : "vcc");
-  // fold the carry as 2^256 = 0x1000003D1: limbs 0..1 always; the carry into limb 2 goes to a lane
-  // mask (fm_mask_bit's comment) and is propagated only behind the rare branch
+  uint32_t s[8];
+  const uint32_t c = fm_add8(s, a.v, b.v);
+  // fold the carry as 2^256 = 0x1000003D1: limbs 0..1 always; the carry into limb 2 (~2^-30 per call: the
+  // fold into a random 256-bit value) goes to a lane mask and is propagated only behind the rare branch
   uint32_t k;
   uint64_t c2;
   asm("v_mul_u32_u24_e32 %2, 0x3d1, %4\n\t"
@@ -661,30 +613,8 @@ FM_DEV void fm_add_lazy(Fe& r, const Fe& a, const Fe& b) {
 
 // a + b mod p, a, b < p, canonical result
 FM_DEV void fm_add(Fe& r, const Fe& a, const Fe& b) {
-  uint32_t s[8], c;
-  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
-      KHB_NOP
-      "v_addc_co_u32_e32 %8, vcc, 0, %25, vcc"
-      : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]), "=&v"(s[6]), "=&v"(s[7]),
-        "=&v"(c)
-      : "v"(a.v[0]), "v"(a.v[1]), "v"(a.v[2]), "v"(a.v[3]), "v"(a.v[4]), "v"(a.v[5]), "v"(a.v[6]), "v"(a.v[7]),
-        "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7]),
-        "v"(0u)
-      : "vcc");
+  uint32_t s[8];
+  const uint32_t c = fm_add8(s, a.v, b.v);
   uint32_t t[8];
   const uint32_t ct = fm_add_k(t, s);
   const bool sel = (c | ct) != 0;    // a+b >= p  <=>  carry out of a+b or of (a+b mod 2^256)+K

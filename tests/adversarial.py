@@ -1,13 +1,14 @@
 """Directed inputs for the rare-carry, canonicalisation and degenerate paths (test infrastructure).
 
-Four things live here, all on Python integers:
+Four things live here, all on Python integers (P, K, limbs, value come from tests/field_model.py):
 
   * secp256k1 affine arithmetic and finders of curve points whose x (or y) falls in a class that the
     lazy field arithmetic of csrc/device/fe_asm.hpp treats specially;
-  * a limb-level model of that arithmetic (fm_reduce, fm_reduce_add, fm_reduce_T, fm_sub, fm_add_lazy,
-    fm_canon) that mirrors the header's decomposition (T, P_i, R, top, u, w, w2) and reports which rare
-    branch a given operand needs.  The model is never the expected value of a test: it chooses operands
-    and certifies that each one arithmetically requires the branch it is aimed at;
+  * the limb-level model of that arithmetic by the names its users know (MODEL, m_mul .. m_canon, flags): thin
+    names over tests/field_model.py, which holds the model of the header as it computes today and the integer
+    definition of every raw lazy value.  The model chooses operands, certifies that each one arithmetically
+    requires the branch it is aimed at, and is what the raw-mode GPU tests compare the device's value with;
+    field_model.check pins it to the integers;
   * planting: start points such that a chosen step of a chosen group of the walk lands on a chosen point,
     the reference's rule for a group's centre, a reference of one -m address group from a centre (degenerate
     groups included) and of one launch of a job as the library splits it over lanes;
@@ -18,10 +19,10 @@ from __future__ import annotations
 
 import random
 
-P = 2**256 - 2**32 - 977
+from tests.field_model import EXACT, K, M32, P, device, limbs, value  # noqa: F401
+from tests.field_model import canon as m_canon, propagate as _propagate  # noqa: F401
+
 N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
-K = 2**32 + 977                      # 2^256 mod p
-M32 = 0xFFFFFFFF
 GROUP = 1024
 HALF = 512
 
@@ -145,155 +146,33 @@ def class_points(cls: str, n: int, seed: int = 0) -> list:
                 return out
 
 
-# ------------------------------------------------------------- limb-level model of device/fe_asm.hpp
+# ------------------------------------------------ the limb-level model of device/fe_asm.hpp, by its old names
+# tests/field_model.py holds the model (device) and the integer definition of every raw value (lazy).
 
-def limbs(v: int, n: int = 8) -> list:
-    return [(v >> (32 * i)) & M32 for i in range(n)]
-
-
-def value(w) -> int:
-    return sum(x << (32 * i) for i, x in enumerate(w))
-
-
-def _propagate(r: list, k: int, c: int) -> int:
-    """fm_propagate<K>: r[k..7] += c, carry-out returned."""
-    for i in range(k, 8):
-        t = r[i] + c
-        r[i] = t & M32
-        c = t >> 32
-    return c
+def _product_op(op: int):
+    def model(a: int, b: int = 0):
+        r, f = device(op, a, b)
+        return r, f["c3"], f["wrap"]
+    return model
 
 
-def m_reduce_T(T: list, H: list):
-    """fm_reduce_T: T (10 words, T9:T8 <= 2^32 + 1) + 977*H -> (lazy value, c3, wrap)."""
-    Pi = [977 * H[i] + T[i] for i in range(8)]
-    R = [Pi[0] & M32]
-    c = 0
-    for i in range(1, 8):
-        t = (Pi[i] & M32) + (Pi[i - 1] >> 32) + c
-        R.append(t & M32)
-        c = t >> 32
-    t = T[8] + (Pi[7] >> 32) + c
-    R8, c = t & M32, t >> 32
-    t = T[9] + c
-    R9 = t & M32
-    assert t >> 32 == 0 and (R9 << 32 | R8) < 3 * 2**32
-    u = R8 * 977 + (((R9 * 977) & M32) << 32)
-    w = ((u >> 32) & M32) + R8
-    w2 = ((w >> 32) + R9) & M32
-    t = R[0] + (u & M32)
-    R[0], c = t & M32, t >> 32
-    t = R[1] + (w & M32) + c
-    R[1], c = t & M32, t >> 32
-    t = R[2] + w2 + c
-    R[2], c3 = t & M32, t >> 32
-    wrap = 0
-    if c3:
-        wrap = _propagate(R, 3, c3)
-        t = R[0] + wrap * 977
-        R[0] = t & M32
-        t = R[1] + wrap + (t >> 32)
-        R[1] = t & M32
-        _propagate(R, 2, t >> 32)
-    return value(R), c3, wrap
-
-
-def m_reduce(t: int):
-    """fm_reduce of a 512-bit product: T = L + (H << 32) as 10 words."""
-    L, H = limbs(t & (2**256 - 1)), limbs(t >> 256)
-    T = [L[0]]
-    c = 0
-    for i in range(1, 8):
-        s = L[i] + H[i - 1] + c
-        T.append(s & M32)
-        c = s >> 32
-    s = H[7] + c
-    T.append(s & M32)
-    T.append(s >> 32)
-    return m_reduce_T(T, H)
-
-
-def m_reduce_add(t: int, w: int):
-    """fm_reduce_add: T = (L + w) + (H << 32), w < 2^256."""
-    L, H, W = limbs(t & (2**256 - 1)), limbs(t >> 256), limbs(w)
-    U = []
-    c = 0
-    for i in range(8):
-        s = L[i] + W[i] + c
-        U.append(s & M32)
-        c = s >> 32
-    U.append(c)
-    T = [U[0]]
-    c = 0
-    for i in range(1, 9):
-        s = U[i] + H[i - 1] + c
-        T.append(s & M32)
-        c = s >> 32
-    T.append(c)
-    return m_reduce_T(T, H)
-
-
-def m_mul(a: int, b: int):
-    return m_reduce(a * b)
-
-
-def m_sqr(a: int, _b: int = 0):
-    return m_reduce(a * a)
-
-
-def m_sqr_add(a: int, w: int):
-    return m_reduce_add(a * a, w)
+m_mul, m_sqr, m_sqr_add = _product_op(0), _product_op(1), _product_op(6)
 
 
 def m_sub(a: int, b: int):
     """fm_sub(a < 2^256, b < p) -> (value, sub_b2)."""
-    A, B = limbs(a), limbs(b)
-    d = []
-    bo = 0
-    for i in range(8):
-        t = A[i] - B[i] - bo
-        d.append(t & M32)
-        bo = 1 if t < 0 else 0
-    m = M32 if bo else 0
-    t = d[0] - (m & 0x3D1)
-    d[0], bo = t & M32, (1 if t < 0 else 0)
-    t = d[1] - (m & 1) - bo
-    d[1], b2 = t & M32, (1 if t < 0 else 0)
-    bo = b2
-    for i in range(2, 8):
-        t = (d[i] - bo) & M32
-        bo = 1 if (bo and d[i] == 0) else 0
-        d[i] = t
-    return value(d), b2
+    r, f = device(3, a, b)
+    return r, f["sub_b2"]
 
 
 def m_add_lazy(a: int, b: int):
     """fm_add_lazy(a < p, b < 2^256) -> (value, lazy_c2)."""
-    A, B = limbs(a), limbs(b)
-    s = []
-    c = 0
-    for i in range(8):
-        t = A[i] + B[i] + c
-        s.append(t & M32)
-        c = t >> 32
-    t = s[0] + 0x3D1 * c
-    s[0] = t & M32
-    t = s[1] + c + (t >> 32)
-    s[1], c2 = t & M32, t >> 32
-    _propagate(s, 2, c2)
-    return value(s), c2
+    r, f = device(5, a, b)
+    return r, f["lazy_c2"]
 
 
-def m_canon(a: int) -> int:
-    """fm_canon: a + K carries out of 2^256 iff a >= p."""
-    t = a + K
-    return t & (2**256 - 1) if t >> 256 else a
-
-
-# field self-test op numbers (include/khbsgs.h khb_field_op) -> model, exact value
+# field self-test op numbers (include/khbsgs.h khb_field_op) -> model
 MODEL = {0: m_mul, 1: m_sqr, 3: m_sub, 5: m_add_lazy, 6: m_sqr_add}
-EXACT = {0: lambda a, b: a * b % P, 1: lambda a, b: a * a % P, 3: lambda a, b: (a - b) % P,
-         5: lambda a, b: (a + b) % P, 6: lambda a, b: (a * a + b) % P}
 
 
 def flags(op: int, a: int, b: int) -> dict:

@@ -1,6 +1,7 @@
-"""Limb-level model of the 512-bit products of csrc/device/fe_asm.hpp with forward-carried columns (fm_mul512x and
-the cross sum of fm_sqr512x), and operands aimed at the columns' edge conditions (test infrastructure; used by
-test_field_columns_model.py and test_gpu_field_columns.py).
+"""Operands aimed at the edge conditions of the forward-carried columns of csrc/device/fe_asm.hpp's 512-bit products
+(fm_mul512x and the cross sum of fm_sqr512x), and the bound that says which columns are masked (test infrastructure;
+used by test_field_columns_model.py and test_gpu_field_directed.py).  The column model itself is
+tests/field_model.py's (cols_mul, cols_cross, cols_sqr, product); this is what it does:
 
 Column K accumulates in one 64-bit pair S that starts as {lo = hi(S of column K-1), hi = cw of column K-1}, where cw
 counts the carries out of the pair.  The first product of a column is added without a carry count.  That is exact
@@ -28,14 +29,12 @@ from __future__ import annotations
 import random
 
 from tests import adversarial as adv
+from tests.field_model import K, M32, M64, M256, MUL_MASKED, P, PMAX, SQR_MASKED  # noqa: F401
+from tests.field_model import cols_cross, cols_mul, cols_sqr  # noqa: F401
+from tests.field_model import cross_products as _cross_products, mul_products as _mul_products
 
-P, K, M32 = adv.P, adv.K, adv.M32
-M64, M256 = 2**64 - 1, 2**256 - 1
-PMAX = (2**32 - 1) ** 2
 MUL_FULL_COLS = tuple(range(2, 13))
 SQR_FULL_COLS = tuple(range(5, 10))
-MUL_MASKED = tuple(range(3, 14))          # fm_mul512x's m[0..10]
-SQR_MASKED = tuple(range(6, 11))          # fm_sqr512x's m[0..4]
 
 
 def unsafe_columns(counts) -> list:
@@ -47,75 +46,6 @@ def unsafe_columns(counts) -> list:
             out.append(k)
         v = (n * PMAX + v) >> 32
     return out
-
-
-def _columns(products, masked):
-    """products[K]: the (x, y) limb pairs of column K, in the device's order; masked: the columns whose first product
-    may drop a carry.  (t[0..15], hi[K], cw[K], total[K], first[K]): hi and cw are what column K hands on, total its
-    unreduced sum, seed included, first the dropped carry of its first product."""
-    t, his, cws, totals, first = [], [], [], [], []
-    hi = cw = 0
-    for k, col in enumerate(products):
-        S = (cw << 32) | hi
-        cw = 0
-        total = S
-        drop = 0
-        for n, (x, y) in enumerate(col):
-            S += x * y
-            total += x * y
-            if n == 0:
-                drop = S >> 64
-                assert drop == 0 or k in masked, "an unmasked column's first product overflowed its seed"
-            else:
-                cw += S >> 64
-            S &= M64
-        t.append(S & M32)
-        hi = S >> 32
-        his.append(hi)
-        cws.append(cw)
-        totals.append(total)
-        first.append(drop)
-    assert cw == 0
-    t.append(hi)                          # column 14's high word is t[15]
-    if any(first):                        # fm_fix_cols: the carry out of column K weighs 2^(32(K+2))
-        v = adv.value(t) + sum(d << (32 * (k + 2)) for k, d in enumerate(first))
-        assert v >> 512 == 0
-        t = adv.limbs(v, 16)
-    return t, his, cws, totals, first
-
-
-def _mul_products(A, B):
-    return [[(A[i], B[k - i]) for i in range(max(0, k - 7), min(k, 7) + 1)] for k in range(15)]
-
-
-def _cross_products(A):
-    return [[(A[i], A[k - i]) for i in range(max(0, k - 7), (k - 1) // 2 + 1)] for k in range(15)]
-
-
-def cols_mul(a: int, b: int):
-    """fm_mul512x: (t, hi, cw, total, first) of the columns of a*b."""
-    return _columns(_mul_products(adv.limbs(a), adv.limbs(b)), MUL_MASKED)
-
-
-def cols_cross(a: int):
-    """The cross sum of fm_sqr512x, sum_{i<j} a_i a_j 2^(32(i+j)): (c, hi, cw, total, first); c[0] = c[15] = 0."""
-    r = _columns(_cross_products(adv.limbs(a)), SQR_MASKED)
-    assert r[0][0] == 0 and r[0][15] == 0
-    return r
-
-
-def cols_sqr(a: int):
-    """fm_sqr512x: t = diagonal + 2 cross as 16 words (the device's funnel shifts and one carry chain)."""
-    c = adv.value(cols_cross(a)[0])
-    d = sum(x * x << (64 * i) for i, x in enumerate(adv.limbs(a)))
-    t = d + 2 * c
-    assert t >> 512 == 0
-    return adv.limbs(t, 16)
-
-
-def t_op(op: int, a: int, b: int) -> int:
-    """The 512-bit product khb_field_op ops 0 (mul), 1 (sqr), 6 (sqr_add) reduce, through the column model."""
-    return adv.value(cols_mul(a, b)[0]) if op == 0 else adv.value(cols_sqr(a))
 
 
 # ------------------------------------------------------------------------------------- operands

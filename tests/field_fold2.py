@@ -1,13 +1,12 @@
-"""Limb-level model of fm_reduce_V's second fold as csrc/device/fe_asm.hpp now computes it, and operands aimed at
-each of its rare conditions (test infrastructure; used by test_field_fold2_model.py and test_gpu_field_fold2.py).
+"""Operands aimed at each rare condition of fm_reduce_V's second fold in csrc/device/fe_asm.hpp (test infrastructure;
+used by test_field_fold2_model.py and test_gpu_field_directed.py).
 
 After the chain R = sum_i lo64(V_i) 2^(32i) + Lw8 2^256 the device keeps R9, the carry out of R8, as a lane mask
 (r9) and folds R8 alone: m = R8 977 + (R1:R0) in one 64-bit multiply-add (carry-out o), R1' = hi(m) + R8,
 R2' = R2 + carry (carry-out c2).  A wave in which any lane has a V carry-out (ov), r9, o or c2 redoes the fold in its
-general form (field_reduce.v_reduce's) for all its lanes.  f_reduce does that per operand and returns the raw lazy
-value with the flags: path ("fast" or "general"), r9, o, c2 as the device computes them (on R before the carry
-fix), and ov.  The device has one rare branch, not one ahead of the common form and one behind it, so "general" stands
-for both.  The common form with a register pair is the one kept; the form without a pair, and its flag wov, do not exist.
+general form for all its lanes.  tests/field_model.py's device() (f_op here) does that per operand and returns the raw
+lazy value with the flags: path ("fast" or "general"), r9, o, c2 as the device computes them (on R before the carry
+fix), and ov.  The device has one rare branch, so "general" stands for every reason to take it.
 
 Operands.  Each generator keeps an operand only when the model raises exactly the flags asked for.
   op 6 (a^2 + w): every flag, by the choice of w for an a whose square has a chosen high half: w sets all of Lw.
@@ -18,125 +17,20 @@ Operands.  Each generator keeps an operand only when the model raises exactly th
         S = d^2 + K d + 2^254 K, a quadratic in d solved mod 2^96 by lifting bit by bit; limb 3 of d is free (ov).
   Not reached for ops 0 and 1: o together with c2 (it needs R8 >= 2^32 - 976, and these families have R8 < 2^31), and
   r9 together with o or c2 (the general fold's concern, covered by op 6's generators and field_reduce's classes).
-fm_add_lazy (op 5) and fm_sub (op 3) keep their carry into limb 2 in a lane mask as well; f_add_lazy / f_sub model
-that form and adversarial.directed_operands provides their classes (lazy_c2, sub_b2)."""
+fm_add_lazy (op 5) and fm_sub (op 3) keep their carry into limb 2 in a lane mask as well; device() models that form
+and adversarial.directed_operands provides their classes (lazy_c2, sub_b2)."""
 from __future__ import annotations
 
 import random
 
 from tests import adversarial as adv
 from tests import field_reduce as fr
+from tests.field_model import K, M32, M64, M256, P  # noqa: F401
+from tests.field_model import device as f_op
 
-P, K, M32 = adv.P, adv.K, adv.M32
-M64, M96, M256 = 2**64 - 1, 2**96 - 1, 2**256 - 1
+M96 = 2**96 - 1
 R9_H7 = (2**32 - 979, 2**32 - 978)       # H_7 that brings R8 to the brink without a V carry-out
 
-
-def _general_fold(R: list, R8: int, R9: int):
-    """fm_fold2: R[7..0] += (R9:R8) (2^32 + 977) with the carry into limb 3 and the wrap.  (c3, wrap)."""
-    u = R8 * 977 + (((R9 * 977) & M32) << 32)
-    ww = ((u >> 32) & M32) + R8
-    w2 = ((ww >> 32) + R9) & M32
-    s = R[0] + (u & M32)
-    R[0], c = s & M32, s >> 32
-    s = R[1] + (ww & M32) + c
-    R[1], c = s & M32, s >> 32
-    s = R[2] + w2 + c
-    R[2], c3 = s & M32, s >> 32
-    wrap = 0
-    if c3:
-        wrap = adv._propagate(R, 3, c3)
-        s = R[0] + wrap * 977
-        R[0] = s & M32
-        s = R[1] + wrap + (s >> 32)
-        R[1] = s & M32
-        adv._propagate(R, 2, s >> 32)
-    return c3, wrap
-
-
-def f_reduce(t: int, w=None):
-    """The raw value the new fm_reduce (w is None) / fm_reduce_add return for the 512-bit t, and the flags."""
-    lw = (t & M256) + (w or 0)
-    Lw8, h = lw >> 256, t >> 256
-    ov, R, c = [], [], 0                 # c: hi(V_{i-1}) + the chain's carry, < 2^33
-    for i in range(8):
-        hi = (h >> (32 * i)) & M32
-        v = 977 * hi + ((hi << 32) | ((lw >> (32 * i)) & M32))
-        ov.append(v >> 64)
-        s = (v & M32) + c
-        R.append(s & M32)
-        c = ((v >> 32) & M32) + (s >> 32)
-    s = Lw8 + c
-    R8, r9 = s & M32, s >> 32
-    assert r9 in (0, 1)
-    # common form, on R as the chain left it
-    m = R8 * 977 + (R[1] << 32 | R[0])
-    o, m = m >> 64, m & M64
-    s = (m >> 32) + R8
-    n1, c = s & M32, s >> 32
-    s = R[2] + c
-    n2, c2 = s & M32, s >> 32
-    flags = {"path": "fast", "r9": r9, "o": o, "c2": c2, "ov": ov, "c3": 0, "wrap": 0}
-    if any(ov) or r9 or o or c2:
-        flags["path"] = "general"
-        R9 = r9
-        if any(ov):
-            c = 0
-            for i in range(8):
-                s = (R[i + 2] if i < 6 else (R8, R9)[i - 6]) + ov[i] + c
-                c = s >> 32
-                if i < 6:
-                    R[i + 2] = s & M32
-                elif i == 6:
-                    R8 = s & M32
-                else:
-                    R9 = s & M32
-            assert c == 0
-        assert (R9 << 32 | R8) < 3 * 2**32
-        flags["c3"], flags["wrap"] = _general_fold(R, R8, R9)
-    else:
-        R[0], R[1], R[2] = m & M32, n1, n2
-    return adv.value(R), flags
-
-
-def f_op(op: int, a: int, b: int):
-    """khb_field_op ops 0 (mul), 1 (sqr), 6 (sqr_add) through the model."""
-    if op == 0:
-        return f_reduce(a * b)
-    return f_reduce(a * a) if op == 1 else f_reduce(a * a, b)
-
-
-def f_add_lazy(a: int, b: int):
-    """fm_add_lazy with the carry into limb 2 as a mask: (value, c2)."""
-    s = a + b
-    c, s = s >> 256, adv.limbs(s & M256)
-    t = s[0] + 0x3D1 * c
-    s[0] = t & M32
-    t = s[1] + c + (t >> 32)
-    s[1], c2 = t & M32, t >> 32
-    if c2:                               # the rare branch: the mask's bit, propagated from limb 2
-        adv._propagate(s, 2, 1)
-    return adv.value(s), c2
-
-
-def f_sub(a: int, b: int):
-    """fm_sub with the borrow into limb 2 as a mask: (value, b2)."""
-    d = a - b
-    bo, d = int(d < 0), adv.limbs(d & M256)
-    t = d[0] - (0x3D1 if bo else 0)
-    d[0], br = t & M32, int(t < 0)
-    t = d[1] - bo - br
-    d[1], b2 = t & M32, int(t < 0)
-    if b2:
-        br = 1
-        for i in range(2, 8):
-            t = d[i] - br
-            d[i], br = t & M32, int(t < 0)
-    return adv.value(d), b2
-
-
-MODEL = {0: lambda a, b: f_op(0, a, b), 1: lambda a, b: f_op(1, a, b), 6: lambda a, b: f_op(6, a, b),
-         5: f_add_lazy, 3: f_sub}
 
 # ------------------------------------------------------------------------------------- operands
 

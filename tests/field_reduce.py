@@ -1,93 +1,23 @@
-"""Limb-level model of the per-limb reduction of csrc/device/fe_asm.hpp (fm_reduce_V) and operands aimed at
-its carry-out branch (test infrastructure; used by test_field_reduce_model.py and test_gpu_field_reduce.py).
+"""Operands aimed at the carry-out branch of the per-limb reduction of csrc/device/fe_asm.hpp (fm_reduce_V)
+(test infrastructure; used by test_field_reduce_model.py and test_gpu_field_directed.py).
 
 The reduction folds S = Lw + Lw8 2^256 + H (2^32 + 977) (L, H the halves of the 512-bit product, Lw = L or
 L + w) through V_i = 977 H_i + (H_i : Lw_i), one 64-bit multiply-add per limb.  V_i can pass 2^64; the
 device keeps the low 64 bits, records the carry-out per lane (ov_i), runs its chain R on the truncated
-values and, when any lane of a wave carried, adds ov_i back at word i + 2 of R.  The model does the same on
-Python integers and returns the raw lazy value with the flags (ov[0..7], c3, wrap)."""
+values and, when any lane of a wave carried, adds ov_i back at word i + 2 of R.  tests/field_model.py models
+that (v_op here is its device()) and gives ov_i from the integers alone (expected_ov)."""
 from __future__ import annotations
 
 import math
 import random
 
 from tests import adversarial as adv
-
-P, K, M32 = adv.P, adv.K, adv.M32
-M64 = 2**64 - 1
-M256 = 2**256 - 1
+from tests.field_model import K, M32, M64, M256, P, expected_ov  # noqa: F401
+from tests.field_model import device as v_op
 # V_i = H_i K + Lw_i >= 2^64: always for H_i >= 2^32 - 976, never for H_i <= 2^32 - 978, and for
 # H_i = 2^32 - 977 (H_i K = 2^64 - 977^2) exactly when Lw_i >= 977^2.
 H_ALWAYS = 2**32 - 976
 EDGE = (2**32 - 979, 2**32 - 978, 2**32 - 977, 2**32 - 976)
-
-
-def v_reduce(t: int, w=None):
-    """The raw value fm_reduce (w is None) / fm_reduce_add return for the 512-bit t, and the flags."""
-    L, H = adv.limbs(t & M256), adv.limbs(t >> 256)
-    Lw, Lw8 = L, 0
-    if w is not None:
-        u = (t & M256) + w
-        Lw, Lw8 = adv.limbs(u & M256), u >> 256
-    V, ov = [], []
-    for i in range(8):
-        v = 977 * H[i] + ((H[i] << 32) | Lw[i])
-        ov.append(v >> 64)
-        V.append(v & M64)
-    assert all(o in (0, 1) for o in ov)
-    R = [V[0] & M32]
-    c = 0
-    for i in range(1, 8):
-        s = (V[i] & M32) + (V[i - 1] >> 32) + c
-        R.append(s & M32)
-        c = s >> 32
-    s = Lw8 + (V[7] >> 32) + c
-    R.append(s & M32)
-    R.append(s >> 32)
-    if any(ov):                                   # the wave-uniform fix: R[i + 2] += ov[i], one chain
-        c = 0
-        for i in range(8):
-            s = R[i + 2] + ov[i] + c
-            R[i + 2] = s & M32
-            c = s >> 32
-        assert c == 0
-    assert adv.value(R) == (t & M256) + (w or 0) + (t >> 256) * K
-    R8, R9 = R[8], R[9]
-    assert (R9 << 32 | R8) < 3 * 2**32
-    R = R[:8]
-    # second fold, as fm_reduce_V: top*977 at limb 0, top*2^32 at limb 1
-    u = R8 * 977 + (((R9 * 977) & M32) << 32)
-    ww = ((u >> 32) & M32) + R8
-    w2 = ((ww >> 32) + R9) & M32
-    s = R[0] + (u & M32)
-    R[0], c = s & M32, s >> 32
-    s = R[1] + (ww & M32) + c
-    R[1], c = s & M32, s >> 32
-    s = R[2] + w2 + c
-    R[2], c3 = s & M32, s >> 32
-    wrap = 0
-    if c3:
-        wrap = adv._propagate(R, 3, c3)
-        s = R[0] + wrap * 977
-        R[0] = s & M32
-        s = R[1] + wrap + (s >> 32)
-        R[1] = s & M32
-        adv._propagate(R, 2, s >> 32)
-    return adv.value(R), {"ov": ov, "c3": c3, "wrap": wrap}
-
-
-def v_op(op: int, a: int, b: int):
-    """khb_field_op ops 0 (mul), 1 (sqr), 6 (sqr_add) through the model."""
-    if op == 0:
-        return v_reduce(a * b)
-    return v_reduce(a * a) if op == 1 else v_reduce(a * a, b)
-
-
-def expected_ov(op: int, a: int, b: int) -> list:
-    """The carry-out of each V mad from the integers alone: H_i K + Lw_i >= 2^64."""
-    t = a * b if op == 0 else a * a
-    lw = (t & M256) + (b if op == 6 else 0)
-    return [int(((t >> (256 + 32 * i)) & M32) * K + ((lw >> (32 * i)) & M32) >= 2**64) for i in range(8)]
 
 
 # ------------------------------------------------------------------------------------- operands

@@ -1,4 +1,4 @@
-"""The column model of tests/field_columns.py against Python integers, and its directed operands: the model's 16
+"""The column model of tests/field_model.py against Python integers, and field_columns' directed operands: the model's 16
 words are a*b / a*a, the masked columns are exactly those whose first product can overflow its seed, every directed
 operand sets the condition it is named for, and every mask and every column that can end with a full high word and a
 carry count has operands of its own."""
@@ -10,6 +10,7 @@ import pytest
 
 from tests import adversarial as adv
 from tests import field_columns as fc
+from tests import field_model as fm
 
 
 def _operands():
@@ -32,7 +33,7 @@ def test_model_is_the_product():
         assert all(c[2][k] == 0 for k in (0, 1, 2, 12, 13, 14))
         assert adv.value(fc.cols_sqr(a)) == a * a
         for op in (0, 1, 6):
-            assert fc.t_op(op, a, b) == (a * b if op == 0 else a * a)
+            assert fm.product(op, a, b)[0] ==(a * b if op == 0 else a * a)
 
 
 def test_all_ones_reaches_every_maximum():
@@ -59,7 +60,7 @@ def test_first_drop_operands(op):
         assert len(ops) == 4
         for a, b in ops:
             assert fc.drops(op, a, b) == [k]
-            assert fc.t_op(op, a, b) == (a * b if op == 0 else a * a)
+            assert fm.product(op, a, b)[0] ==(a * b if op == 0 else a * a)
 
 
 def test_low_ones_reach_each_count():
@@ -89,7 +90,7 @@ def test_full_high_operands(op):
         assert len(ops) == 4
         for a, b in ops:
             assert fc.is_full_high(op, a, b, k)
-            assert fc.t_op(op, a, b) == (a * b if op == 0 else a * a)
+            assert fm.product(op, a, b)[0] ==(a * b if op == 0 else a * a)
 
 
 def test_directed_lists():

@@ -1,8 +1,8 @@
 """The per-limb reduction of fe_asm.hpp (V_i = 977 H_i + (H_i : Lw_i), carry-outs added back at word i + 2)
-as a limb model (tests/field_reduce.py) against the limb model of the T = L + (H << 32) form it replaces
-(tests/adversarial.py, read only): the raw lazy value and the c3 / wrap flags must be equal for ops 0, 1, 6
-on 100,000 random operands and on every directed class, and each directed operand must raise the carry-out
-flags it is aimed at."""
+as the limb model of tests/field_model.py against the integer definition of the lazy value (field_model.lazy):
+the raw value and the c3 / wrap / ov flags must be equal for ops 0, 1, 6 on 100,000 random operands and on
+every directed class of tests/field_reduce.py, and each directed operand must raise the carry-out flags it is
+aimed at."""
 from __future__ import annotations
 
 import random
@@ -10,18 +10,14 @@ import random
 import pytest
 
 from tests import adversarial as adv
+from tests import field_model as fm
 from tests import field_reduce as fr
 
 OPS = (0, 1, 6)
 
 
 def _same(op, a, b):
-    r, f = fr.v_op(op, a, b)
-    m = adv.MODEL[op](a, b)
-    assert (r, f["c3"], f["wrap"]) == m, (op, a, b)
-    assert f["ov"] == fr.expected_ov(op, a, b), (op, a, b)
-    assert r % adv.P == adv.EXACT[op](a, b) and r < 2**256
-    return f
+    return fm.check(op, a, b)[1]          # value, c3, wrap, ov equal the integers'; < 2^256; congruent
 
 
 @pytest.mark.parametrize("op", OPS)
