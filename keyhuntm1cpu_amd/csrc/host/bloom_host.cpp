@@ -10,23 +10,6 @@ void words_of_bytes32(uint64_t w[4], const uint8_t x[32]) {
   for (int k = 0; k < 4; ++k) memcpy(&w[k], x + 8 * k, 8);   // little-endian host, XXH_readLE64
 }
 
-int BloomFilter::init2(uint64_t n_entries, long double err, bool alloc) {
-  *this = BloomFilter();
-  if (n_entries < 1000 || err <= 0 || err >= 1) return 1;
-  entries = n_entries;
-  error = err;
-  const long double num = -logl(error);
-  const long double denom = 0.480453013918201;   // ln(2)^2 as the reference spells it
-  bpe = (double)(num / denom);
-  const long double allbits = (long double)entries * bpe;
-  bits = (uint64_t)allbits;
-  bytes = bits / 8 + ((bits % 8) ? 1 : 0);
-  hashes = (uint8_t)ceil(0.693147180559945 * bpe);
-  if (alloc) bf.assign(bytes, 0);
-  ready = true;
-  return 0;
-}
-
 BloomGeom BloomFilter::geom() const {
   BloomGeom g;
   g.bytes_per_sub = bytes;

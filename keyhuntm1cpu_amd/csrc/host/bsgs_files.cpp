@@ -182,4 +182,21 @@ bool Tables::save_files(const std::string& dir, uint32_t have, std::string& err,
   return true;
 }
 
+bool Tables::obtain(const Geometry& g, const TableSource& src, uint32_t* have_out, std::string& err) {
+  uint32_t have = 0;
+  resident = src.resident;
+  if (src.dir) {
+    prepare(g);
+    if (!load_files(src.dir, src.skip_checksum, have, err, src.say)) return false;
+    if (src.after_load) src.after_load(have);
+  }
+  const bool all_read = have == kFileAll;   // giant tables and lane offsets only, unless the gate is walked
+  const int device = all_read && !src.gate_walk_when_all_read ? -1 : src.device;
+  if (!build(g, src.threads, src.gpl, err, all_read ? nullptr : src.progress, have, device)) return false;
+  if (!all_read && src.after_build) src.after_build(have);
+  if (src.dir && src.save && !all_read && !save_files(src.dir, have, err, src.say)) return false;
+  if (have_out) *have_out = have;
+  return true;
+}
+
 }  // namespace khb

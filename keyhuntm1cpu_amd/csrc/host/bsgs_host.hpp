@@ -39,6 +39,25 @@ struct XValue {            // struct bsgs_xvalue, keyhunt.cpp:70-73
 // 8 = L3 _7_<m3>.blm.
 enum : uint32_t { kFileL1 = 1, kFileL2 = 2, kFileBp = 4, kFileL3 = 8, kFileAll = 15 };
 
+// Where Tables::obtain gets a geometry's tables from, and what it tells its caller on the way.
+struct TableSource {
+  const char* dir = nullptr;             // -S: the table files' directory; nullptr: no file is read or written
+  bool skip_checksum = false;            // -6
+  bool save = true;                      // write the files that were not read (with dir)
+  int threads = 1;
+  uint32_t gpl = 4;                      // GPU groups per lane of the lane offsets
+  int device = -1;                       // baby steps on this GPU; -1: on the CPU
+  bool resident = false;                 // Tables::resident (no dir, a device)
+  // With every file read no baby step is left to walk, and build() has no level-0 gate to fill: the search then
+  // probes the level-1 bloom ungated.  Set, `device` walks the level-1 extent once more for the gate alone.
+  // bsgsd_amd sets it, keyhunt_amd -S and khh_tables_new_files do not.
+  bool gate_walk_when_all_read = false;
+  std::function<void(const std::string&)> say;            // the "[+] Reading ..." / "[+] Writing ..." lines
+  std::function<void(uint64_t, uint64_t)> progress;       // build() progress, when a baby step is walked
+  // the caller's own lines: after the files were read, and after a build that walked baby steps (before "Writing")
+  std::function<void(uint32_t have)> after_load, after_build;
+};
+
 struct Tables {
   Geometry geo;
   std::vector<BloomFilter> l1, l2, l3;   // 256 sub-blooms each
@@ -100,6 +119,9 @@ struct Tables {
   bool save_files(const std::string& dir, uint32_t have, std::string& err,
                   const std::function<void(const std::string&)>& log) const;
   static std::string file_name(const Geometry& g, uint32_t which);
+  // The whole sequence: load_files (with src.dir), build what they did not hold, save_files.  *have: the kFile*
+  // mask read.
+  bool obtain(const Geometry& g, const TableSource& src, uint32_t* have, std::string& err);
   std::vector<uint8_t> l1_concat() const;
   std::vector<uint8_t> bloom_concat(int level) const;    // level 1..3: 256 sub-blooms concatenated
   std::vector<uint8_t> amp_table_be(int level) const;    // level 2, 3: BSGS_AMP2 / BSGS_AMP3, 32 x||y BE

@@ -20,10 +20,10 @@
 #include <unistd.h>
 
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "bsgs_host.hpp"
+#include "cli.hpp"
 #include "engine.hpp"
 
 using namespace khb;
@@ -49,27 +49,6 @@ void menu() {
   exit(EXIT_FAILURE);
 }
 
-bool valid_hex(const char* s) {   // util.c:169-178
-  for (; *s; ++s) {
-    const char c = *s;
-    if (!((c >= '0' && c <= '9') || (c >= 'A' && c <= 'F') || (c >= 'a' && c <= 'f'))) return false;
-  }
-  return true;
-}
-
-// stringtokenizer (util.c:67-84): trim "\t\n\r :" then strtok on " \t:"
-std::vector<std::string> tokenize(std::string s) {
-  const char* trimset = "\t\n\r :";
-  size_t b = s.find_first_not_of(trimset), e = s.find_last_not_of(trimset);
-  if (b == std::string::npos) return {};
-  s = s.substr(b, e - b + 1);
-  std::vector<std::string> out;
-  std::vector<char> buf(s.begin(), s.end());
-  buf.push_back(0);
-  for (char* tok = strtok(buf.data(), " \t:"); tok; tok = strtok(nullptr, " \t:")) out.push_back(tok);
-  return out;
-}
-
 void send_str(int fd, const std::string& s) {
   if (send(fd, s.data(), s.size(), 0) == -1) printf("Failed to send message to client\n");
 }
@@ -84,7 +63,7 @@ void handle(int fd, Session& S, const Tables& T) {
   n = recv(fd, buffer, line_length, 0);
   if (n <= 0) return;
   buffer[n] = 0;
-  const std::vector<std::string> t = tokenize(buffer);
+  const std::vector<std::string> t = tokens(buffer);
   if (t.size() != 3) {
     printf("Invalid input format from client, tokens %i : %s\n", (int)t.size(), buffer);
     send_str(fd, "400 Bad Request");
@@ -123,100 +102,56 @@ int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOLBF, 0);
   signal(SIGPIPE, SIG_IGN);
   printf("[+] Version %s\n", kVersion);
-  int kfactor = 1, nthreads = (int)std::thread::hardware_concurrency(), port = 8080;
-  bool skip_checksum = false, cpu_build = false, resident = false;
-  const char* str_n = nullptr;
+  int port = 8080;
   std::string ip = "127.0.0.1";
-  SearchConfig cfg;
-  if (nthreads > 16) nthreads = 16;
-  static struct option longopts[] = {{"cpu-build", no_argument, nullptr, 1000},
-                                     {"check", required_argument, nullptr, 1001},
-                                     {"resident", no_argument, nullptr, 1002},
+  CliOptions o;   // the options shared with keyhunt_amd, and -n
+  static struct option longopts[] = {{"cpu-build", no_argument, nullptr, kOptCpuBuild},
+                                     {"check", required_argument, nullptr, kOptCheck},
+                                     {"resident", no_argument, nullptr, kOptResident},
                                      {nullptr, 0, nullptr, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "6hk:n:t:p:i:g:", longopts, nullptr)) != -1) {
+    if (parse_shared_option(c, optarg, o)) continue;
     switch (c) {
-      case '6': skip_checksum = true; fprintf(stderr, "[W] Skipping checksums on files\n"); break;
       case 'h': menu(); break;
-      case 'k':
-        kfactor = (int)strtol(optarg, nullptr, 10);
-        if (kfactor <= 0) kfactor = 1;
-        printf("[+] K factor %i\n", kfactor);
-        break;
-      case 'n': str_n = optarg; break;
-      case 't':
-        nthreads = (int)strtol(optarg, nullptr, 10);
-        if (nthreads <= 0) nthreads = 1;
-        printf(nthreads > 1 ? "[+] Threads : %u\n" : "[+] Thread : %u\n", nthreads);
-        break;
+      case 'n': o.str_n = optarg; break;
       case 'p':
         port = (int)strtol(optarg, nullptr, 10);
         if (port <= 0 || port > 65535) port = 8080;
         break;
       case 'i': ip = optarg; break;
-      case 'g': {
-        cfg.devices.clear();
-        std::string part;
-        for (const char* p = optarg;; ++p) {
-          if (*p == ',' || *p == 0) {
-            if (!part.empty()) cfg.devices.push_back(atoi(part.c_str()));
-            part.clear();
-            if (!*p) break;
-          } else {
-            part.push_back(*p);
-          }
-        }
-        if (cfg.devices.empty()) cfg.devices.push_back(0);
-        break;
-      }
-      case 1000: cpu_build = true; break;
-      case 1001:                                    // where candidates are confirmed (engine.hpp check_mode)
-        if ((cfg.check_mode = parse_check_mode(optarg)) < 0) {
-          fprintf(stderr, "[E] --check: host, gpu or auto\n");
-          exit(EXIT_FAILURE);
-        }
-        break;
-      case 1002: resident = true; break;
       default:
         fprintf(stderr, "[E] Unknow opcion -%c\n", c);
         exit(0);
     }
   }
-  if (resident && cpu_build) {
-    fprintf(stderr, "[E] --resident builds the level-1 bloom on the GPU and keeps it there: it cannot be combined with --cpu-build\n");
-    exit(EXIT_FAILURE);
-  }
+  check_resident_conflict(o);
   printf("[+] Mode BSGS secuential\n");
   Geometry geo;
   std::string err;
-  if (!make_geometry(str_n, kfactor, geo, err)) {
+  if (!make_geometry(o.str_n, o.kfactor, geo, err)) {
     fprintf(stderr, "%s\n", err.c_str());
     exit(EXIT_FAILURE);
   }
   printf("[+] N = 0x%s\n", geo.N.hex().c_str());
-  {
-    auto mb = [](uint64_t bytes) { return (float)bytes / 1048576.0f; };
-    BloomFilter b;
-    b.init2(geo.items1, 0.000001, false);
-    printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m, mb(b.bytes * 256));
-    b.init2(geo.items2, 0.000001, false);
-    printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m2, mb(b.bytes * 256));
-    b.init2(geo.items3, 0.000001, false);
-    printf("[+] Bloom filter for %llu elements : %.2f MB\n", (unsigned long long)geo.m3, mb(b.bytes * 256));
-    printf("[+] Allocating %.2f MB for %llu bP Points\n", (double)(geo.m3 * 16 / 1048576), (unsigned long long)geo.m3);
-  }
+  print_table_sizes(geo);
   Tables T;
-  auto say = [](const std::string& m) { printf("%s", m.c_str()); fflush(stdout); };
-  uint32_t have = 0;
-  T.prepare(geo);
-  T.resident = resident;               // no table files: the level-1 bloom exists on the GPUs only
-  if ((!resident && !T.load_files(".", skip_checksum, have, err, say)) ||
-      !T.build(geo, nthreads, 4, err, nullptr, have, cpu_build ? -1 : cfg.devices[0]) ||
-      (!resident && have != kFileAll && !T.save_files(".", have, err, say))) {
+  TableSource src;
+  src.dir = o.resident ? nullptr : ".";   // resident: no table files, the level-1 bloom exists on the GPUs only
+  src.skip_checksum = o.skip_checksum;
+  src.threads = o.threads;
+  src.device = o.cpu_build ? -1 : o.devices[0];
+  src.resident = o.resident;
+  src.gate_walk_when_all_read = true;
+  src.say = [](const std::string& m) { printf("%s", m.c_str()); fflush(stdout); };
+  if (!T.obtain(geo, src, nullptr, err)) {
     fprintf(stderr, "%s\n", err.c_str());
     exit(EXIT_FAILURE);
   }
-  cfg.check_threads = nthreads;
+  SearchConfig cfg;
+  cfg.devices = o.devices;
+  cfg.check_mode = o.check_mode;
+  cfg.check_threads = o.threads;
   Session S;
   if (S.open(T, cfg, err)) {
     fprintf(stderr, "[E] %s\n", err.c_str());

@@ -419,13 +419,6 @@ void device_thread(Shared& S, khb_ctx* ctx) {
 
 }  // namespace
 
-int parse_check_mode(const char* s) {
-  if (!strcmp(s, "host")) return kCheckHost;
-  if (!strcmp(s, "gpu")) return kCheckDevice;
-  if (!strcmp(s, "auto")) return kCheckAuto;
-  return -1;
-}
-
 int load_check_tables(khb_ctx* c, const Tables& T) {
   const std::vector<uint8_t> l2 = T.bloom_concat(2), l3 = T.bloom_concat(3);
   const std::vector<uint8_t> a2 = T.amp_table_be(2), a3 = T.amp_table_be(3);
@@ -551,20 +544,6 @@ int Session::set_test_hooks(uint32_t cand_cap, bool use_gate, const uint8_t* l1_
   cfg_.cand_cap = cand_cap;
   cfg_.use_gate = use_gate;
   return 0;
-}
-
-void print_resident_lines(const Session& s) {
-  const std::vector<Session::ResidentInfo>& v = s.resident_info();
-  for (size_t i = 0; i < v.size(); ++i) {
-    const double mb = 1.0 / 1048576.0;
-    char gate[96] = "no gate";
-    if (v[i].gate_log2)
-      snprintf(gate, sizeof gate, "gate 2^%u bits (%.2f MB, %u probes)", v[i].gate_log2,
-               (double)(1ull << (v[i].gate_log2 - 3)) * mb, v[i].gate_probes);
-    printf("[+] GPU %d resident: L1 bloom %.2f MB, %s, build %.1f ms\n", s.config().devices[i],
-           (double)v[i].l1_bytes * mb, gate, v[i].build_ms);
-  }
-  fflush(stdout);
 }
 
 int Session::set_check_mode(int mode) {

@@ -57,8 +57,6 @@ enum : int { kCheckHost = 0, kCheckDevice = 1, kCheckAuto = 2 };
 // uniform base in the range), dance (4794-5068: top, bottom or a uniform base between them, at random).
 enum : int { kChunkSequential = 0, kChunkBackward = 1, kChunkBoth = 2, kChunkRandom = 3, kChunkDance = 4 };
 constexpr uint32_t kCheckAutoMin = 4096;
-// The --check argument of keyhunt_amd / bsgsd_amd: "host", "gpu" or "auto"; -1 for anything else.
-int parse_check_mode(const char* s);
 
 // The chunk bases of one search in claim order (keyhunt's BSGS_CURRENT / n_range_end under bsgs_thread),
 // for a -B mode (kChunk*); the seed drives the both / dance side choices.  Shared by every device thread
@@ -147,10 +145,6 @@ class Session {
   std::vector<ResidentInfo> resident_;
   bool gate_dropped_ = false;  // resident: set_test_hooks(use_gate = false) freed the gate; only a new open rebuilds it
 };
-
-// --resident: one "[+] GPU <d> resident: L1 ..., gate ..., build ..." line per device of an open session (nothing
-// on other tables).
-void print_resident_lines(const Session& s);
 
 // The check tables of T (level-2/3 blooms, bPtable, AMP2/AMP3, GTable, M constants) into a context.
 int load_check_tables(khb_ctx* c, const Tables& T);

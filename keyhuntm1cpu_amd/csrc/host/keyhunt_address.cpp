@@ -5,9 +5,7 @@
 #include <string.h>
 
 #include <atomic>
-#include <chrono>
 #include <mutex>
-#include <thread>
 
 #include "../../../include/khbsgs.h"
 #include "address_host.hpp"
@@ -30,16 +28,9 @@ void writekey(const AddrFound& f, std::mutex& mu, bool xpoint = false) {
   const std::string addr = rmd_to_address(rmd.data());
   char rmdhex[41];
   for (int i = 0; i < 20; ++i) snprintf(rmdhex + 2 * i, 3, "%02x", rmd[i]);
-  std::lock_guard<std::mutex> lk(mu);
-  FILE* keys = fopen("KEYFOUNDKEYFOUND.txt", "a+");
-  if (keys) {
-    fprintf(keys, "Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", hexkey.c_str(), pubhex.c_str(), addr.c_str(),
-            rmdhex);
-    fclose(keys);
-  }
-  printf("\nHit! Private Key: %s\npubkey: %s\nAddress %s\nrmd160 %s\n", hexkey.c_str(), pubhex.c_str(), addr.c_str(),
-         rmdhex);
-  fflush(stdout);
+  const std::string text =
+      "Private Key: " + hexkey + "\npubkey: " + pubhex + "\nAddress " + addr + "\nrmd160 " + rmdhex + "\n";
+  append_found(mu, text, "\nHit! " + text);
 }
 
 // writekeyeth (keyhunt.cpp:6023-6051)
@@ -47,20 +38,29 @@ void writekeyeth(const AddrFound& f, std::mutex& mu) {
   const std::string hexkey = f.key.hex();
   char address[43] = "0x";
   for (int i = 0; i < 20; ++i) snprintf(address + 2 + 2 * i, 3, "%02x", f.rmd[i]);
-  std::lock_guard<std::mutex> lk(mu);
-  FILE* keys = fopen("KEYFOUNDKEYFOUND.txt", "a+");
-  if (keys) {
-    fprintf(keys, "Private Key: %s\naddress: %s\n", hexkey.c_str(), address);
-    fclose(keys);
-  }
-  printf("\n Hit!!!! Private Key: %s\naddress: %s\n", hexkey.c_str(), address);
-  fflush(stdout);
+  const std::string text = "Private Key: " + hexkey + "\naddress: " + address + "\n";
+  append_found(mu, text, "\n Hit!!!! " + text);
 }
 
 }  // namespace
 
-int run_address_mode(const AddressCli& o) {
-  if (!o.crypto_set && o.mode == 1) printf("[+] Setting search for btc adddress\n");   // keyhunt.cpp:812-815
+int run_address_mode(const CliOptions& o) {
+  const bool xpoint = o.mode == kModeXpoint;
+  if (o.eth && o.mode != kModeAddress) {   // -c is "valid only w/ -m address"
+    fprintf(stderr, "[E] -c eth is valid only with -m address (-m %s)\n",
+            xpoint ? "xpoint searches public-key x values" : "rmd160 searches BTC hash160 values");
+    return EXIT_FAILURE;
+  }
+  if (o.eth && o.endomorphism) {
+    // keyhunt.cpp:2772 hashes beta*x a second time where beta^2*x was meant and recovers that slot with
+    // lambda^2, so the reference's -c eth -e can print a key that does not own the address
+    fprintf(stderr, "[E] -c eth does not work with -e: the reference's ETH endomorphism path hashes beta*x twice "
+                    "(beta^2*x is never hashed) and can report a key that does not own the address; it is not "
+                    "reproduced\n");
+    return EXIT_FAILURE;
+  }
+  const CliRange range = resolve_range(o);   // keyhunt.cpp:816-838
+  if (!o.crypto_set && o.mode == kModeAddress) printf("[+] Setting search for btc adddress\n");   // keyhunt.cpp:812-815
   U256 stride(1);
   if (o.stride) {   // keyhunt.cpp:790-797
     const bool ok = (o.stride[0] == '0' && o.stride[1] == 'x') ? U256::from_hex(o.stride + 2, stride)
@@ -74,9 +74,9 @@ int run_address_mode(const AddressCli& o) {
   const char* file = o.file ? o.file : "addresses.txt";   // default_fileName
   // range (keyhunt.cpp:844-864)
   U256 start(1), end = secp_order();
-  if (o.have_range) {
-    start = o.start;
-    end = o.end;
+  if (range.have) {
+    start = range.start;
+    end = range.end;
   } else if (o.flag_bits) {
     U256::from_hex(o.bits_min.c_str(), start);
     U256::from_hex(o.bits_max.c_str(), end);
@@ -102,7 +102,6 @@ int run_address_mode(const AddressCli& o) {
   // targets (keyhunt.cpp:6300-6358, 6559-6576)
   AddrTargets T;
   std::string err;
-  const bool xpoint = o.mode == 0;
   if (!AddrTargets::load_file(file, o.bloom_multiplier, T, &err,
                               xpoint ? kTargetsXpoint : o.eth ? kTargetsEth : kTargetsBtc)) {
     fprintf(stderr, "[E] %s\n[E] Unenexpected error\n", err.c_str());
@@ -127,13 +126,12 @@ int run_address_mode(const AddressCli& o) {
   cfg.start = start;
   cfg.end = end;
   cfg.n_seq = n_seq;
-  cfg.random = o.random;
+  cfg.random = o.bsgs_mode == kBsgsRandom;   // -R
   cfg.devices = o.devices;
-  cfg.lanes = o.lanes;
+  cfg.lanes = o.gpu_blocks * 256u;
   cfg.gpl = gpl;
   cfg.max_chunks = o.max_chunks;
   std::mutex out_mu;
-  std::atomic<bool> done{false};
   AddrStats stats;
   std::atomic<uint64_t> keys_done{0};
   AddrCallbacks cb;
@@ -150,24 +148,11 @@ int run_address_mode(const AddressCli& o) {
   };
   // stats line every -s seconds (keyhunt.cpp:2145-2252): keys = groups * 1024, x6 with -e (keyhunt.cpp:2175-2180:
   // every -l mode; x3 for -m xpoint), else x2 for -l compress
-  std::thread stat_th([&] {
-    const auto t0 = std::chrono::steady_clock::now();
-    uint64_t sec = 0;
-    while (!done.load()) {
-      std::this_thread::sleep_for(std::chrono::milliseconds(100));
-      const uint64_t s = (uint64_t)std::chrono::duration_cast<std::chrono::seconds>(
-                             std::chrono::steady_clock::now() - t0).count();
-      if (s == sec) continue;
-      sec = s;
-      if (o.out_seconds && s % o.out_seconds == 0) {
-        U256 total(keys_done.load());
-        if (o.endomorphism) total = total * (xpoint ? 3u : 6u);   // keyhunt.cpp:2175-2181
-        else if (o.search == 1) total = total * 2u;   // also with -c eth, as the reference (keyhunt.cpp:2183-2186)
-        std::lock_guard<std::mutex> lk(out_mu);
-        printf("\r%s\r", speed_line(total, s).c_str());
-        fflush(stdout);
-      }
-    }
+  StatsTicker ticker(o.out_seconds, false, out_mu, [&](uint64_t seconds) {
+    U256 total(keys_done.load());
+    if (o.endomorphism) total = total * (xpoint ? 3u : 6u);   // keyhunt.cpp:2175-2181
+    else if (o.search == 1) total = total * 2u;   // also with -c eth, as the reference (keyhunt.cpp:2183-2186)
+    return speed_line(total, seconds);
   });
   AddrCallbacks cb2 = cb;
   cb2.on_chunk = [&](const U256& base, int device) {
@@ -175,8 +160,7 @@ int run_address_mode(const AddressCli& o) {
     keys_done.fetch_add(n_seq);
   };
   const int rc = addr_search(T, G, cfg, cb2, &stats, &err);
-  done.store(true);
-  stat_th.join();
+  ticker.stop();
   if (rc) {
     fprintf(stderr, "[E] %s\n", err.c_str());
     return EXIT_FAILURE;

@@ -37,76 +37,56 @@ extern "C" {
 
 int khh_abi_version(void) { return KHH_ABI_VERSION; }
 
-khh_tables* khh_tables_new(const char* n_str, int k, int threads, uint32_t gpl, char* err, size_t errlen) {
+// The khh_tables_new* constructors: geometry, Tables::obtain from src (threads and gpl defaulted here), and the
+// results they hand back.  resident_gate: khh_tables_new_resident's explicit gate size.
+static khh_tables* tables_new(const char* n_str, int k, int threads, uint32_t gpl, TableSource src,
+                              uint32_t resident_gate, uint32_t* have, double* kernel_ms, char* err, size_t errlen) {
   Geometry g;
   std::string e;
   if (!make_geometry(n_str, k, g, e)) { set_err(err, errlen, e); return nullptr; }
-  khh_tables* t = new khh_tables();
-  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-  if (!t->t.build(g, threads, gpl ? gpl : 4, e)) {
-    set_err(err, errlen, e);
-    delete t;
-    return nullptr;
-  }
-  return t;
-}
-
-khh_tables* khh_tables_new_files(const char* n_str, int k, int threads, uint32_t gpl, const char* dir,
-                                 int skip_checksum, int save, uint32_t* have, char* err, size_t errlen) {
-  Geometry g;
-  std::string e;
-  if (!make_geometry(n_str, k, g, e)) { set_err(err, errlen, e); return nullptr; }
-  khh_tables* t = new khh_tables();
-  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-  uint32_t h = 0;
-  t->t.prepare(g);
-  if (!t->t.load_files(dir ? dir : ".", skip_checksum != 0, h, e, nullptr) ||
-      !t->t.build(g, threads, gpl ? gpl : 4, e, nullptr, h) ||
-      (save && h != kFileAll && !t->t.save_files(dir ? dir : ".", h, e, nullptr))) {
-    set_err(err, errlen, e);
-    delete t;
-    return nullptr;
-  }
-  if (have) *have = h;
-  return t;
-}
-
-khh_tables* khh_tables_new_gpu(const char* n_str, int k, int threads, uint32_t gpl, int device, double* kernel_ms,
-                               char* err, size_t errlen) {
-  Geometry g;
-  std::string e;
-  if (!make_geometry(n_str, k, g, e)) { set_err(err, errlen, e); return nullptr; }
-  khh_tables* t = new khh_tables();
-  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-  if (!t->t.build(g, threads, gpl ? gpl : 4, e, nullptr, 0, device)) {
-    set_err(err, errlen, e);
-    delete t;
-    return nullptr;
-  }
-  if (kernel_ms) *kernel_ms = t->t.build_gpu_ms;
-  return t;
-}
-
-khh_tables* khh_tables_new_resident(const char* n_str, int k, int threads, uint32_t gpl, int device,
-                                    uint32_t gate_log2, double* kernel_ms, char* err, size_t errlen) {
-  Geometry g;
-  std::string e;
-  if (!make_geometry(n_str, k, g, e)) { set_err(err, errlen, e); return nullptr; }
-  if (gate_log2 && (gate_log2 < 13 || gate_log2 > 38)) {
+  if (resident_gate && (resident_gate < 13 || resident_gate > 38)) {
     set_err(err, errlen, "[E] resident gate size: 0 or 13..38 (log2 bits)");
     return nullptr;
   }
   khh_tables* t = new khh_tables();
-  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-  t->t.resident = true;
-  t->t.resident_gate = gate_log2;
-  if (!t->t.build(g, threads, gpl ? gpl : 4, e, nullptr, 0, device)) {
+  src.threads = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+  src.gpl = gpl ? gpl : 4;
+  t->t.resident_gate = resident_gate;
+  if (!t->t.obtain(g, src, have, e)) {
     set_err(err, errlen, e);
     delete t;
     return nullptr;
   }
   if (kernel_ms) *kernel_ms = t->t.build_gpu_ms;
   return t;
+}
+
+khh_tables* khh_tables_new(const char* n_str, int k, int threads, uint32_t gpl, char* err, size_t errlen) {
+  return tables_new(n_str, k, threads, gpl, TableSource(), 0, nullptr, nullptr, err, errlen);
+}
+
+khh_tables* khh_tables_new_files(const char* n_str, int k, int threads, uint32_t gpl, const char* dir,
+                                 int skip_checksum, int save, uint32_t* have, char* err, size_t errlen) {
+  TableSource src;
+  src.dir = dir ? dir : ".";
+  src.skip_checksum = skip_checksum != 0;
+  src.save = save != 0;
+  return tables_new(n_str, k, threads, gpl, src, 0, have, nullptr, err, errlen);
+}
+
+khh_tables* khh_tables_new_gpu(const char* n_str, int k, int threads, uint32_t gpl, int device, double* kernel_ms,
+                               char* err, size_t errlen) {
+  TableSource src;
+  src.device = device;
+  return tables_new(n_str, k, threads, gpl, src, 0, nullptr, kernel_ms, err, errlen);
+}
+
+khh_tables* khh_tables_new_resident(const char* n_str, int k, int threads, uint32_t gpl, int device,
+                                    uint32_t gate_log2, double* kernel_ms, char* err, size_t errlen) {
+  TableSource src;
+  src.device = device;
+  src.resident = true;
+  return tables_new(n_str, k, threads, gpl, src, gate_log2, nullptr, kernel_ms, err, errlen);
 }
 
 int khh_tables_is_resident(const khh_tables* t) { return t && t->t.resident ? 1 : 0; }

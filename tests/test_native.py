@@ -70,3 +70,19 @@ def test_confirm_header_on_host_sanitized(tmp_path):
     probes at both ends of the table and the byte windows of ck_mul_g stay inside their arrays."""
     out = _build_and_run("test_confirm_host.cpp", tmp_path, sanitize=True)
     assert out.strip().endswith("ok"), out
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitized"])
+def test_cli_parse_layer_on_host(tmp_path, sanitize):
+    """host/cli.cpp (the option parser of keyhunt_amd and bsgsd_amd, the -r rule, -g, tokens, valid_hex) as a
+    stand-alone program built from cli.cpp, u256.cpp and secp_host.cpp alone; the second run under the host
+    AddressSanitizer and UBSan.  Needs neither the oracle objects nor a GPU."""
+    host = os.path.join(REPO, "keyhuntm1cpu_amd", "csrc", "host")
+    exe = str(tmp_path / "test_cli_host")
+    subprocess.run(["g++", *(SANITIZE if sanitize else ["-O2"]), "-std=c++17", "-pthread",
+                    os.path.join(HERE, "native", "test_cli_host.cpp"), *(os.path.join(host, f) for f in
+                                                                         ("cli.cpp", "u256.cpp", "secp_host.cpp")),
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().endswith("ok"), r.stdout
