@@ -349,6 +349,59 @@ int khb_load_vanity(khb_ctx* ctx, const uint8_t* lo_be20, const uint8_t* hi_be20
  * scan kernels' own match (bitmap copied to LDS, then vanity_match).  KHB_ESTATE before khb_load_vanity. */
 int khb_vanity_match(khb_ctx* ctx, const uint8_t* h20, uint8_t* hit, uint32_t n);
 
+/* ---- -m minikeys (thread_process_minikeys, keyhunt.cpp:2338-2505) ----
+ * A candidate is 'S' followed by 21 characters of a 58-character alphabet; its 21 digits (values 0..57, digit 0 the
+ * most significant) count in [0, 58^21), and character j + 1 is alphabet[digit j].  It is valid iff byte 0 of
+ * SHA-256(minikey || '?') is 0; its private key is SHA-256(minikey) read big-endian; it is a hit iff the hash160 of
+ * that key's uncompressed public key passes the -m address bloom (khb_load_addr_bloom).  A launch examines the
+ * candidates first, first + 1, ..., first + count - 1 exactly once each: a filter kernel queues the offsets of the
+ * valid ones on the device, a second kernel computes key, point (k*G over the window table below), hash and bloom
+ * for each queued offset.  A key that is 0 or >= the group order has no public key: it is counted (bad_keys) and is
+ * never a hit.
+ * Additions to ABI 7, as the -m vanity calls were: no existing signature or struct changed, so the version stays 7;
+ * a caller checks for the khb_load_mini_table symbol.
+ *
+ * The window table: for window width w = window_bits (4, 8 or 16), the affine points d * 2^(w j) * G for
+ * j = 0 .. 256/w - 1 and d = 1 .. 2^w - 1 in that order (point j * (2^w - 1) + d - 1), 64 bytes x||y BE each:
+ * 64 x 15, 32 x 255 or 16 x 65,535 points (60 KiB, 510 KiB, 64 MiB).  A load replaces the previous table. */
+int khb_load_mini_table(khb_ctx* ctx, const uint8_t* points_xy_be, uint32_t window_bits);
+typedef struct {
+  uint64_t offset;          /* of the candidate from `first` */
+  uint8_t h160[20];         /* hash160 of its key's uncompressed public key */
+} khb_mini_hit;
+typedef struct {
+  uint64_t candidates;      /* the launch's count */
+  uint64_t valid;           /* candidates that passed the typo check (counted past the queue's capacity) */
+  uint64_t bad_keys;        /* valid candidates whose key is 0 or >= n */
+  uint64_t hits;            /* bloom hits (counted past the ring's capacity) */
+  uint32_t queue_overflow;  /* 1: valid > the survivor queue's capacity, the keys of the rest were not examined */
+  uint32_t hit_overflow;    /* 1: hits > khb_addr_hit_capacity(), the rest were not kept */
+  float filter_ms;          /* the filter kernel, by HIP events; -1 if unavailable */
+  float keys_ms;            /* the key, point and match kernel */
+} khb_mini_stats;
+/* first_digits: 21 digit values; alphabet: 58 distinct bytes; 1 <= count <= 2^32 (the queues hold 32-bit offsets; a
+ * caller cuts a longer span into launches) and first + count <= 58^21 (no wrap), KHB_EINVAL otherwise.  KHB_ESTATE
+ * before khb_load_mini_table and khb_load_addr_bloom; nothing is launched in either case.  One launch is in flight at
+ * a time per context, and none while a scan of another kind is (KHB_EBUSY).  After either overflow flag the caller
+ * rescans the span in parts: the flagged launch's hits are incomplete. */
+int khb_mini_submit(khb_ctx* ctx, const uint8_t* first_digits, uint64_t count, const uint8_t* alphabet);
+int khb_mini_collect(khb_ctx* ctx, khb_mini_hit* hits, uint32_t cap, khb_mini_stats* stats);
+int khb_mini_scan(khb_ctx* ctx, const uint8_t* first_digits, uint64_t count, const uint8_t* alphabet,
+                  khb_mini_hit* hits, uint32_t cap, khb_mini_stats* stats);
+/* Survivor-queue entries of later launches: 0 (the default) sizes it from the launch, count / 64 + 1024, four times
+ * the expected count / 256; any other value is for tests of the caller's overflow path.  The hit ring is the
+ * -m address one: khb_addr_hit_capacity(), lowered by khb_set_candidate_capacity. */
+int khb_mini_set_queue_capacity(khb_ctx* ctx, uint32_t cap);
+uint32_t khb_mini_queue_capacity(const khb_ctx* ctx, uint64_t count);
+/* self-test: the filter kernel alone.  *n_out = the number of valid candidates of the span, and up to cap of their
+ * offsets from `first` (unordered, as the queue holds them) in offsets_out.  Needs no table and no bloom. */
+int khb_mini_filter(khb_ctx* ctx, const uint8_t* first_digits, uint64_t count, const uint8_t* alphabet,
+                    uint64_t* offsets_out, uint32_t cap, uint64_t* n_out);
+/* self-test: k*G over the loaded table for n caller-supplied 32-byte BE scalars, through the search kernel's own
+ * device functions.  flags_out[i] = 1 for a bad key (0 or >= n), whose xy_out is 64 zero bytes.  KHB_ESTATE before
+ * khb_load_mini_table. */
+int khb_mini_pubkey(khb_ctx* ctx, const uint8_t* scalars_be, uint8_t* xy_out, uint8_t* flags_out, uint32_t n);
+
 /* ---- baby-step tables on the GPU (thread_bPload, keyhunt.cpp:4404-4592; orchestration 1615-1880) ----
  * Uses the loaded giant table as Gn[i] = (i+1)*G, _2Gn = 1024*G and the lane offsets for jobs of
  * groups_per_job groups.  Job k covers baby steps ic = k*groups_per_job*1024 + [0, groups_per_job*1024)

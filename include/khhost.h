@@ -25,8 +25,10 @@ extern "C" {
  * ABI 9 added -m xpoint: khh_addr_new_xpoint, khh_addr_counted, search = KHB_SEARCH_XPOINT (optionally with
  * KHB_SEARCH_ENDOMORPHISM) and khh_addr_confirm's kinds KHB_ADDR_KIND_X | e << 2.
  * ABI 10 added -m vanity: khh_addr_new_vanity, khh_addr_vanity_intervals, khh_addr_vanity_match and
- * khh_vanity_target_ok. */
-#define KHH_ABI_VERSION 10
+ * khh_vanity_target_ok.
+ * ABI 11 added -m minikeys: khh_mini_new / khh_mini_free, khh_mini_search, khh_mini_string, khh_mini_valid,
+ * khh_mini_key, khh_mini_table and khh_mini_set_queue_capacity / khh_mini_set_hit_capacity. */
+#define KHH_ABI_VERSION 11
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -269,6 +271,54 @@ void khh_hash160(const uint8_t xy[64], int compressed, uint8_t out[20]);
 void khh_rmd_to_address(const uint8_t rmd[20], char* out_addr);
 /* ETH address of a public key (x||y BE; any 64 bytes): bytes 12..31 of Keccak-256(x||y), keyhunt.cpp:4783-4789 */
 void khh_eth_address(const uint8_t xy[64], uint8_t out[20]);
+
+/* ---- -m minikeys (thread_process_minikeys, keyhunt.cpp:2338-2505) ----
+ * A minikey is 'S' and 21 characters of a 58-character alphabet; the 21 characters are the digits of a counter in
+ * [0, 58^21), the first the most significant.  It is valid iff byte 0 of SHA-256(minikey || '?') is zero; its private
+ * key is SHA-256(minikey) read big-endian; it is a find iff the hash160 of that key's uncompressed public key is a
+ * target.  A search examines first, first + 1, ..., first + count - 1, each exactly once.  Two deliberate deviations
+ * from the reference: its cycles step by 253 N candidates but run until N valid keys were seen, so they overlap or
+ * leave gaps at random (keyhunt.cpp:897-917, 2430-2501), and it increments before its first test, so the base it
+ * prints is never tested; here a span is exact and `first` is tested.
+ *
+ * text: the target file's contents, read as -m address reads it (BTC addresses or 40-hex hash160 lines; the same
+ * bloom, sorted table and skipped / counted numbers as khh_addr_new).  alphabet: 58 distinct non-zero bytes, or NULL
+ * for the reference's Ccoinbuffer_default.  window_bits: 4, 8 or 16, the width of the device's k*G table (0 = the
+ * default, 16: DESIGN.md §2f), built here.  NULL with err on a bad argument. */
+typedef struct khh_mini khh_mini;
+khh_mini* khh_mini_new(const char* text, int bloom_multiplier, const uint8_t* alphabet, uint32_t window_bits,
+                       int threads, char* err, size_t errlen);
+void khh_mini_free(khh_mini* m);
+/* The window table khb_load_mini_table takes (*n_points points of 64 bytes) and its width. */
+const uint8_t* khh_mini_table(const khh_mini* m, uint64_t* n_points, uint32_t* window_bits);
+/* out22 = the minikey `offset` candidates after first22 (22 characters, no terminator).  KHB_EINVAL for a first22
+ * that is no minikey of the handle's alphabet or a sum of 58^21 or more. */
+int khh_mini_string(const khh_mini* m, const char* first22, uint64_t offset, char* out22);
+/* 1 when the 22 characters pass the typo check, 0 when not, KHB_EINVAL when they are no minikey of the alphabet. */
+int khh_mini_valid(const khh_mini* m, const char* minikey22);
+/* out32 = SHA-256 of the 22 characters: the private key, big-endian. */
+void khh_mini_key(const char* minikey22, uint8_t out32[32]);
+/* Tests: survivor-queue and bloom-hit ring capacities of the search's launches (0 = the library's defaults); an
+ * overflowed launch is rescanned in halves. */
+int khh_mini_set_queue_capacity(khh_mini* m, uint32_t cap);
+int khh_mini_set_hit_capacity(khh_mini* m, uint32_t cap);
+/* Examine `count` candidates from first22 (first_len must be 22) on the given devices, in launches of per_launch
+ * candidates (0 = 2^30; at most 2^32).  Every device hit is confirmed by recomputing minikey -> key -> k*G -> hash160
+ * and a lookup in the sorted table.  Finds: minikeys (22 bytes each), keys_be (32), rmd (20), up to cap; *n_found
+ * counts them all.  stats_out[0 .. stats_len) of KHH_MINI_STATS values: candidates, valid, bad_keys, hits (device
+ * bloom hits), launches, rescans, filter kernel us, key/point/match kernel us.  A bad first22 or
+ * first + count > 58^21 is KHB_EINVAL with err, and nothing is launched. */
+#define KHH_MINI_STATS 8
+/* The CPU baseline of a measurement: the reference's loop (keyhunt.cpp:2430-2498: next candidate, SHA-256 of the 23
+ * bytes, and for a valid one SHA-256 of the 22, k*G, hash160 of the uncompressed key, bloom, searchbinary) restated on
+ * the host's own functions over the same exact span, `threads` threads each taking a contiguous part.  *valid and
+ * *found count what it saw; returns the seconds it took, negative on a bad argument. */
+double khh_mini_cpu_scan(const khh_mini* m, const char* first22, uint64_t count, int threads, uint64_t* valid,
+                         uint64_t* found);
+int khh_mini_search(const khh_mini* m, const char* first22, size_t first_len, uint64_t count, const int* devices,
+                    int n_devices, uint32_t lanes, uint64_t per_launch, char* minikeys, uint8_t* keys_be, uint8_t* rmd,
+                    uint32_t cap, uint32_t* n_found, uint64_t* stats_out, uint32_t stats_len, char* err,
+                    size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
 //   khb_tables.hip    table loads, gate stages, baby and resident builds, the resident inspection calls
 //   khb_selftest.hip  field / probe / hash160 self-tests and the point dumps
 //   k_check.hip       the second / third check: its kernel, tables and khb_check
+//   k_mini.hip        -m minikeys: its kernels, table, launch state and the khb_mini_* calls
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +19,7 @@
 namespace khbk {
 struct CheckIn;                        // k_check.hip
 struct CheckOut;
+struct MiniState;                      // k_mini.hip
 }  // namespace khbk
 
 // One submission's device state.  A context owns two (KHB_QUEUE_DEPTH): khb_submit fills the next
@@ -91,6 +93,13 @@ struct khb_ctx {
   // (kVanityBitmapWords words), one allocation; null = none loaded
   uint32_t* d_van = nullptr;
   uint32_t van_n = 0;
+  // -m minikeys (k_mini.hip): the window table of khb_load_mini_table, the launch state (a stream and queues of the
+  // mode's own, allocated on first use) and the survivor queue's capacity (0 = sized from the launch)
+  khb::CPt* d_mini_tab = nullptr;
+  uint32_t mini_w = 0;
+  khbk::MiniState* mini = nullptr;
+  uint32_t mini_queue_cap = 0;
+  bool mini_busy = false;              // a khb_mini_submit is in flight
   // second / third check (khb_load_check_tables, khb_check): tables, a high-priority stream of its own
   // and buffers grown to the largest batch
   khb::CheckTables ck{};
@@ -200,6 +209,8 @@ int check_scan_args(khb_ctx* c, const uint8_t* centres, uint32_t n_jobs, uint32_
                     bool bsgs);
 ScanArgs make_args(khb_ctx* c, const Slot& S, uint32_t n_jobs, uint32_t group_begin, uint32_t group_count,
                    uint32_t per_item = 0);
+// Defined in k_mini.hip: frees the context's -m minikeys state (khb_close).
+void mini_free(khb_ctx* c);
 
 }  // namespace khbk
 #pragma GCC visibility pop

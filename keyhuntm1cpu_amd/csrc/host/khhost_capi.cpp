@@ -10,6 +10,7 @@
 #include "address_host.hpp"
 #include "bsgs_host.hpp"
 #include "engine.hpp"
+#include "mini_host.hpp"
 
 using namespace khb;
 using namespace khbk;   // SearchMode and its decoder (device/scan_modes.hpp)
@@ -24,6 +25,11 @@ struct khh_addr {
   uint64_t n_seq = 0;
   uint32_t hit_cap = 0;      // tests: bloom-hit ring capacity per launch (0 = library default)
   std::vector<uint8_t> van_bytes;   // khh_addr_vanity_intervals: lo || hi of the merged intervals
+};
+
+struct khh_mini {
+  MiniSearch S;
+  uint32_t queue_cap = 0, hit_cap = 0;   // tests: the launches' capacities (0 = library defaults)
 };
 
 static void set_err(char* err, size_t n, const std::string& m) {
@@ -546,6 +552,123 @@ int khh_addr_confirm(const khh_addr* a, const uint8_t key_be[32], uint32_t kind,
 }
 
 void khh_eth_address(const uint8_t xy[64], uint8_t out[20]) { eth_address_xy(xy, out); }
+
+// ---------------------------------------------------------------------------------- -m minikeys
+khh_mini* khh_mini_new(const char* text, int bloom_multiplier, const uint8_t* alphabet, uint32_t window_bits,
+                       int threads, char* err, size_t errlen) {
+  if (!text) {
+    set_err(err, errlen, "no targets");
+    return nullptr;
+  }
+  if (window_bits == 0) window_bits = 16;   // the measured default
+  if (window_bits != 4 && window_bits != 8 && window_bits != 16) {
+    set_err(err, errlen, "window_bits: 4, 8 or 16");
+    return nullptr;
+  }
+  khh_mini* m = new khh_mini();
+  std::string e;
+  if (!m->S.A.set(alphabet)) {
+    set_err(err, errlen, "the alphabet is 58 distinct non-zero bytes");
+    delete m;
+    return nullptr;
+  }
+  if (!AddrTargets::load_text(text, bloom_multiplier, m->S.T, &e, kTargetsBtc)) {
+    set_err(err, errlen, e);
+    delete m;
+    return nullptr;
+  }
+  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+  m->S.window_bits = window_bits;
+  m->S.table = mini_table_be(window_bits, threads);
+  return m;
+}
+
+void khh_mini_free(khh_mini* m) { delete m; }
+
+const uint8_t* khh_mini_table(const khh_mini* m, uint64_t* n_points, uint32_t* window_bits) {
+  if (n_points) *n_points = m ? m->S.table.size() / 64 : 0;
+  if (window_bits) *window_bits = m ? m->S.window_bits : 0;
+  return m ? m->S.table.data() : nullptr;
+}
+
+int khh_mini_string(const khh_mini* m, const char* first22, uint64_t offset, char* out22) {
+  MiniDigits d;
+  if (!m || !first22 || !out22 || !mini_parse(m->S.A, first22, kMiniLen, d, nullptr))
+    return KHB_EINVAL;
+  if (!mini_advance(d, offset)) return KHB_EINVAL;
+  mini_string(m->S.A, d, out22);
+  return KHB_OK;
+}
+
+int khh_mini_valid(const khh_mini* m, const char* minikey22) {
+  MiniDigits d;
+  if (!m || !minikey22 || !mini_parse(m->S.A, minikey22, kMiniLen, d, nullptr))
+    return KHB_EINVAL;
+  return mini_is_valid(minikey22) ? 1 : 0;
+}
+
+void khh_mini_key(const char* minikey22, uint8_t out32[32]) { mini_key_of(minikey22, out32); }
+
+int khh_mini_set_queue_capacity(khh_mini* m, uint32_t cap) {
+  if (!m) return KHB_EINVAL;
+  m->queue_cap = cap;
+  return KHB_OK;
+}
+
+int khh_mini_set_hit_capacity(khh_mini* m, uint32_t cap) {
+  if (!m) return KHB_EINVAL;
+  m->hit_cap = cap;
+  return KHB_OK;
+}
+
+double khh_mini_cpu_scan(const khh_mini* m, const char* first22, uint64_t count, int threads, uint64_t* valid,
+                         uint64_t* found) {
+  MiniDigits first, last;
+  if (!m || !first22 || count == 0 || !mini_parse(m->S.A, first22, kMiniLen, first, nullptr)) return -1.0;
+  last = first;
+  if (!mini_advance(last, count - 1)) return -1.0;
+  return mini_cpu_scan(m->S, first, count, threads, valid, found);
+}
+
+int khh_mini_search(const khh_mini* m, const char* first22, size_t first_len, uint64_t count, const int* devices,
+                    int n_devices, uint32_t lanes, uint64_t per_launch, char* minikeys, uint8_t* keys_be, uint8_t* rmd,
+                    uint32_t cap, uint32_t* n_found, uint64_t* stats_out, uint32_t stats_len, char* err,
+                    size_t errlen) {
+  if (!m) return KHB_EINVAL;
+  std::string e;
+  MiniDigits first;
+  if (!mini_parse(m->S.A, first22, first_len, first, &e)) {
+    set_err(err, errlen, e);
+    return KHB_EINVAL;
+  }
+  MiniConfig cfg;
+  cfg.lanes = lanes;
+  if (per_launch) cfg.per_launch = per_launch;
+  cfg.queue_cap = m->queue_cap;
+  cfg.hit_cap = m->hit_cap;
+  cfg.devices.clear();
+  for (int i = 0; i < n_devices; ++i) cfg.devices.push_back(devices[i]);
+  if (cfg.devices.empty()) cfg.devices.push_back(0);
+  uint32_t nf = 0;
+  auto on_found = [&](const MiniFound& f) {
+    if (nf < cap) {
+      if (minikeys) memcpy(minikeys + (size_t)kMiniLen * nf, f.minikey, kMiniLen);
+      if (keys_be) f.key.to_be(keys_be + 32 * (size_t)nf);
+      if (rmd) memcpy(rmd + 20 * (size_t)nf, f.rmd.data(), 20);
+    }
+    ++nf;
+  };
+  MiniStats st;
+  const int rc = mini_search(m->S, first, count, cfg, on_found, &st, &e);
+  if (n_found) *n_found = nf;
+  if (stats_out) {
+    const uint64_t v[KHH_MINI_STATS] = {st.candidates, st.valid, st.bad_keys, st.hits, st.launches, st.rescans,
+                                        (uint64_t)(st.filter_seconds * 1e6), (uint64_t)(st.keys_seconds * 1e6)};
+    memcpy(stats_out, v, sizeof(uint64_t) * (stats_len < KHH_MINI_STATS ? stats_len : KHH_MINI_STATS));
+  }
+  if (rc) set_err(err, errlen, e);
+  return rc;
+}
 
 void khh_hash160(const uint8_t xy[64], int compressed, uint8_t out[20]) {
   hash160_pub(pt_from_be(xy), compressed != 0, out);

@@ -105,7 +105,7 @@ int upload(khb_ctx* c, T*& dst, const void* src, size_t bytes) {
 int load_bloom(khb_ctx* c, uint8_t*& d, BloomGeom& g, const uint8_t* bf, uint64_t bytes_per_sub, size_t total,
                uint64_t bits, uint32_t hashes) {
   if (!bf || !bloom_args_ok(bytes_per_sub, bits, hashes)) return KHB_EINVAL;
-  if (c->queued) return KHB_EBUSY;
+  if (c->queued || c->mini_busy) return KHB_EBUSY;
   KHB_TRY(c, hipSetDevice(c->device));
   drop_bloom(d, g);
   if (const int rc = upload(c, d, bf, total)) {

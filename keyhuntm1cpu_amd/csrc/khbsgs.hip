@@ -282,6 +282,7 @@ int submit_scan(khb_ctx* c, int kind, const uint8_t* centres, uint32_t n_jobs, u
   if (!bsgs && !decode_search(search, sm)) return KHB_EINVAL;
   if (!(bsgs ? (void*)c->d_bloom : sm.vanity ? (void*)c->d_van : (void*)c->d_abloom)) return KHB_ESTATE;
   if (c->queued && c->slot[c->head].kind != kind) return KHB_EBUSY;     // a scan of the other kind is in flight
+  if (c->mini_busy) return KHB_EBUSY;                                   // or a -m minikeys launch
   KHB_TRY(c, hipSetDevice(c->device));
   Slot* Sp = next_slot(c, rc);
   if (!Sp) return rc;
@@ -509,6 +510,7 @@ int khb_close(khb_ctx* c) {
   hipFree(c->d_gofs);
   hipFree(c->d_abloom);
   hipFree(c->d_van);
+  mini_free(c);
   delete c;
   return KHB_OK;
 }

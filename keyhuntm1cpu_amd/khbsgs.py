@@ -57,6 +57,18 @@ class Stats(C.Structure):
                 ("shader_mhz", C.c_float), ("event_ms", C.c_float)]
 
 
+class MiniHit(C.Structure):        # khb_mini_hit
+    _fields_ = [("offset", C.c_uint64), ("h160", C.c_uint8 * 20)]
+
+
+class MiniStats(C.Structure):      # khb_mini_stats
+    _fields_ = [("candidates", C.c_uint64), ("valid", C.c_uint64), ("bad_keys", C.c_uint64), ("hits", C.c_uint64),
+                ("queue_overflow", C.c_uint32), ("hit_overflow", C.c_uint32), ("filter_ms", C.c_float),
+                ("keys_ms", C.c_float)]
+
+
+MINI_ALPHABET = b"123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"   # the reference's Ccoinbuffer_default
+
 _libs: dict[str, C.CDLL] = {}
 KHB_ABI_VERSION = 7
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
@@ -145,6 +157,20 @@ def lib(path: str | None = None) -> C.CDLL:
         if hasattr(L, "khb_load_vanity"):        # the -m vanity additions to ABI 7
             L.khb_load_vanity.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
             L.khb_vanity_match.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]
+        if hasattr(L, "khb_load_mini_table"):    # the -m minikeys additions to ABI 7
+            L.khb_load_mini_table.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
+            L.khb_addr_hit_capacity.restype = C.c_uint32
+            L.khb_addr_hit_capacity.argtypes = [C.c_void_p]
+            L.khb_mini_submit.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p]
+            L.khb_mini_collect.argtypes = [C.c_void_p, P(MiniHit), C.c_uint32, P(MiniStats)]
+            L.khb_mini_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, P(MiniHit), C.c_uint32,
+                                        P(MiniStats)]
+            L.khb_mini_set_queue_capacity.argtypes = [C.c_void_p, C.c_uint32]
+            L.khb_mini_queue_capacity.restype = C.c_uint32
+            L.khb_mini_queue_capacity.argtypes = [C.c_void_p, C.c_uint64]
+            L.khb_mini_filter.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, P(C.c_uint64), C.c_uint32,
+                                          P(C.c_uint64)]
+            L.khb_mini_pubkey.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
         if hasattr(L, "khb_check"):              # ABI 5
             L.khb_load_check_tables.argtypes = [C.c_void_p, P(CheckTables)]
             L.khb_check.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, P(CheckIn), C.c_uint32, P(CheckOut)]
@@ -415,6 +441,45 @@ class Engine:
         out = C.create_string_buffer(n)
         _check(self.L.khb_vanity_match(self.h, bytes(h20), out, n), self.h, self.L)
         return out.raw
+
+    # ---- -m minikeys ----
+    def load_mini_table(self, points: bytes, window_bits: int) -> None:
+        """The window table of the device's k*G (khhost.Minikeys.table_points): d * 2^(w j) * G, 64 bytes each."""
+        if window_bits in (4, 8, 16):
+            assert len(points) == 64 * (256 // window_bits) * ((1 << window_bits) - 1)
+        _check(self.L.khb_load_mini_table(self.h, points, window_bits), self.h, self.L)
+
+    def set_mini_queue_capacity(self, cap: int) -> None:
+        """Survivor-queue entries of later launches (0 = sized from the launch); for tests of the overflow path."""
+        _check(self.L.khb_mini_set_queue_capacity(self.h, cap), self.h, self.L)
+
+    def mini_scan(self, first_digits: bytes, count: int, alphabet: bytes = MINI_ALPHABET, cap: int = 1 << 18):
+        """Bloom hits [(offset, hash160)] among the candidates first .. first + count - 1 (21 digit values), and the
+        launch's MiniStats.  An overflow flag in the stats means the hits are incomplete."""
+        hits = (MiniHit * cap)()
+        st = MiniStats()
+        _check(self.L.khb_mini_scan(self.h, bytes(first_digits), count, bytes(alphabet), hits, cap, C.byref(st)),
+               self.h, self.L)
+        n = min(st.hits, cap, self.L.khb_addr_hit_capacity(self.h))      # what the ring kept
+        return [(int(hits[i].offset), bytes(hits[i].h160)) for i in range(n)], st
+
+    def mini_filter(self, first_digits: bytes, count: int, alphabet: bytes = MINI_ALPHABET, cap: int = 1 << 20):
+        """The filter kernel alone: (offsets of the valid candidates as the queue holds them, their number)."""
+        out = (C.c_uint64 * max(1, cap))()
+        n = C.c_uint64(0)
+        _check(self.L.khb_mini_filter(self.h, bytes(first_digits), count, bytes(alphabet), out, cap, C.byref(n)),
+               self.h, self.L)
+        return [int(out[i]) for i in range(min(n.value, cap))], int(n.value)
+
+    def mini_pubkey(self, scalars: list[int]) -> list[tuple[bytes, int]]:
+        """[(x||y, bad-key flag)] of k*G over the loaded table for each scalar below 2^256."""
+        n = len(scalars)
+        xy = C.create_string_buffer(64 * n)
+        fl = C.create_string_buffer(n)
+        _check(self.L.khb_mini_pubkey(self.h, b"".join(k.to_bytes(32, "big") for k in scalars), xy, fl, n),
+               self.h, self.L)
+        r, f = xy.raw, fl.raw
+        return [(r[64 * i:64 * i + 64], f[i]) for i in range(n)]
 
     def addr_dump(self, centre: bytes, group_begin: int, group_count: int) -> bytes:
         out = C.create_string_buffer(group_count * KHB_GROUP * 64)

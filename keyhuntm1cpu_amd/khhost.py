@@ -12,8 +12,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 10                # include/khhost.h
+KHH_ABI_VERSION = 11                # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
+KHH_MINI_STATS = 8
+MINI_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"   # Ccoinbuffer_default
 KHH_RESIDENT_INFO = 8
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
 
@@ -128,6 +130,22 @@ def lib() -> C.CDLL:
                                          C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32,
                                          P(C.c_uint32), P(C.c_uint64), C.c_uint32, C.c_char_p, C.c_size_t]
         L.khh_addr_set_hit_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.khh_mini_new.restype = C.c_void_p
+        L.khh_mini_new.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        L.khh_mini_free.argtypes = [C.c_void_p]
+        L.khh_mini_table.restype = P(C.c_uint8)
+        L.khh_mini_table.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint32)]
+        L.khh_mini_string.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p]
+        L.khh_mini_valid.argtypes = [C.c_void_p, C.c_char_p]
+        L.khh_mini_key.restype = None
+        L.khh_mini_key.argtypes = [C.c_char_p, C.c_char_p]
+        L.khh_mini_set_queue_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.khh_mini_set_hit_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.khh_mini_cpu_scan.restype = C.c_double
+        L.khh_mini_cpu_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, P(C.c_uint64), P(C.c_uint64)]
+        L.khh_mini_search.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, P(C.c_int), C.c_int, C.c_uint32,
+                                      C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, P(C.c_uint32),
+                                      P(C.c_uint64), C.c_uint32, C.c_char_p, C.c_size_t]
         L.khh_addr_confirm.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int)]
         L.khh_hash160.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
         L.khh_rmd_to_address.argtypes = [C.c_char_p, C.c_char_p]
@@ -617,6 +635,122 @@ class Addr:
         found = [(int.from_bytes(kb[32 * i:32 * i + 32], "big"), bool(cb[i]), rb[20 * i:20 * i + 20]) for i in range(n)]
         return found, {"chunks": st[0], "keys": st[1], "hits": st[2], "degenerate": st[3], "kernel_s": st[4] / 1e6,
                        "launches": st[5], "shader_mhz": st[6] / 1e3, "rescans": st[7]}
+
+
+class Minikeys:
+    """-m minikeys: targets (a target file's text, read as -m address reads it) and the window table of the device's
+    k*G.  A minikey is 'S' and 21 characters of `alphabet` (58 distinct characters; the reference's by default); a
+    search examines `count` consecutive candidates from `first`, each exactly once, `first` included."""
+
+    def __init__(self, text: str, alphabet: str | bytes | None = None, window_bits: int = 16,
+                 bloom_multiplier: int = 1, threads: int = 0):
+        if window_bits not in (4, 8, 16):
+            raise ValueError("window_bits: 4, 8 or 16")
+        a = alphabet.encode("latin-1") if isinstance(alphabet, str) else alphabet
+        if a is not None and (len(a) != 58 or len(set(a)) != 58 or 0 in a):
+            raise ValueError("alphabet: 58 distinct non-zero characters")
+        self.alphabet = bytes(a) if a is not None else MINI_ALPHABET.encode()
+        err = C.create_string_buffer(256)
+        self.h = lib().khh_mini_new(text.encode(), bloom_multiplier, a, window_bits, threads, err, 256)
+        if not self.h:
+            raise KhhError(err.value.decode())
+        self.window_bits = window_bits
+
+    def close(self) -> None:
+        if self.h:
+            lib().khh_mini_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mk(self, s: str | bytes) -> bytes:
+        b = s.encode("latin-1") if isinstance(s, str) else bytes(s)
+        if len(b) != 22 or b[:1] != b"S" or any(c not in self.alphabet for c in b[1:]):
+            raise ValueError("a minikey is 'S' and 21 characters of the alphabet")
+        return b
+
+    def digits(self, s: str | bytes) -> bytes:
+        """The 21 digit values of a minikey (what khbsgs.Engine.mini_scan takes)."""
+        return bytes(self.alphabet.index(c) for c in self._mk(s)[1:])
+
+    def table_points(self) -> bytes:
+        """The window table khb_load_mini_table takes: d * 2^(w j) * G, 64 bytes x||y each."""
+        n, w = C.c_uint64(0), C.c_uint32(0)
+        p = lib().khh_mini_table(self.h, C.byref(n), C.byref(w))
+        return C.string_at(p, 64 * n.value)
+
+    def string(self, first: str | bytes, offset: int) -> str:
+        """The minikey `offset` candidates after `first`; ValueError past 58^21 - 1."""
+        out = C.create_string_buffer(22)
+        if offset < 0 or offset >= 1 << 64 or lib().khh_mini_string(self.h, self._mk(first), offset, out):
+            raise ValueError("offset out of range")
+        return out.raw.decode("latin-1")
+
+    def valid(self, minikey: str | bytes) -> bool:
+        r = lib().khh_mini_valid(self.h, self._mk(minikey))
+        if r < 0:
+            raise ValueError("not a minikey of this alphabet")
+        return bool(r)
+
+    def key(self, minikey: str | bytes) -> int:
+        out = C.create_string_buffer(32)
+        lib().khh_mini_key(self._mk(minikey), out)
+        return int.from_bytes(out.raw, "big")
+
+    def set_queue_capacity(self, cap: int) -> None:
+        """Tests: the launches' survivor-queue capacity (0 = sized from the launch); overflow -> rescan in halves."""
+        if lib().khh_mini_set_queue_capacity(self.h, cap):
+            raise KhhError("khh_mini_set_queue_capacity")
+
+    def set_hit_capacity(self, cap: int) -> None:
+        """Tests: the launches' bloom-hit ring capacity (0 = default 2^18); overflow -> rescan in halves."""
+        if lib().khh_mini_set_hit_capacity(self.h, cap):
+            raise KhhError("khh_mini_set_hit_capacity")
+
+    def cpu_scan(self, first: str | bytes, count: int, threads: int = 16) -> tuple[float, int, int]:
+        """The reference's loop on the CPU over the same span (a measurement's baseline): (seconds, valid, found)."""
+        v, f = C.c_uint64(0), C.c_uint64(0)
+        dt = lib().khh_mini_cpu_scan(self.h, self._mk(first), count, threads, C.byref(v), C.byref(f))
+        if dt < 0:
+            raise ValueError("cpu_scan: bad span")
+        return float(dt), int(v.value), int(f.value)
+
+    def search(self, first: str | bytes, count: int, devices=(0,), lanes: int = 0, per_launch: int = 0,
+               cap: int = 4096):
+        """Found [(minikey, key, rmd160)] in the order the launches report them (ascending within a launch) and
+        stats.  A bad `first` or first + count > 58^21 is a ValueError."""
+        fb = self._mk(first)
+        if count < 1 or count >= 1 << 64:
+            raise ValueError("count: 1 to 2^64 - 1")
+        mk = C.create_string_buffer(22 * cap)
+        keys = C.create_string_buffer(32 * cap)
+        rmd = C.create_string_buffer(20 * cap)
+        nf = C.c_uint32(0)
+        st = (C.c_uint64 * KHH_MINI_STATS)()
+        devs = (C.c_int * len(devices))(*devices)
+        err = C.create_string_buffer(256)
+        rc = lib().khh_mini_search(self.h, fb, len(fb), count, devs, len(devices), lanes, per_launch, mk, keys, rmd,
+                                   cap, C.byref(nf), st, KHH_MINI_STATS, err, 256)
+        if rc == -1:                    # KHB_EINVAL
+            raise ValueError(f"khh_mini_search: {err.value.decode()}")
+        if rc:
+            raise KhhError(f"khh_mini_search: {err.value.decode()} [{rc}]")
+        n = min(nf.value, cap)
+        mb, kb, rb = mk.raw, keys.raw, rmd.raw
+        found = [(mb[22 * i:22 * i + 22].decode("latin-1"), int.from_bytes(kb[32 * i:32 * i + 32], "big"),
+                  rb[20 * i:20 * i + 20]) for i in range(n)]
+        return found, {"candidates": st[0], "valid": st[1], "bad_keys": st[2], "hits": st[3], "launches": st[4],
+                       "rescans": st[5], "filter_s": st[6] / 1e6, "keys_s": st[7] / 1e6}
 
 
 def resident_gate_log2(l1ext: int, budget_bytes: int) -> int:
