@@ -1,4 +1,4 @@
-// The level-1 probe of the -m bsgs scan: the survivor queue, the gate's tests, probe / probe_pair / gate_pair.
+// The level-1 probe of the -m bsgs scan: the survivor queue, the gate's tests, probe / probe_pair / the gate's phases.
 #pragma once
 #include "scan_args.hpp"
 
@@ -113,46 +113,102 @@ __device__ __forceinline__ uint2 gate_block(const uint8_t* g, uint32_t mask, con
   return reinterpret_cast<const uint2*>(g)[x.v[0] & mask];
 }
 
-// kScanG: gate test of one walk step's two x (x2 absent at step 511: has2 = false, uniform).  Both
-// blocks are loaded before either is waited for; survivors (~0.04 % of x) go to the queue.
-// STAGES (gate_stages): 1 tests the stage-1 fold first, 2 tests the stage-0 filter before the fold.  Each stage
-// is a superset of the next, so the queued x are exactly the full gate's survivors in every case.
+// kScanG: gate test of one walk step's two x (x2 absent at step 511: has2 = false, uniform), in phases, so that the
+// walk runs the next step's field products between a load and its first use instead of waiting out two dependent
+// round trips (the fold from L2, the gate from the Infinity Cache) with nothing to issue:
+//   gate_issue_first   x1's first load, as soon as x1 is finished (x2's product and squaring run behind it);
+//   gate_issue_second  x2's first load;
+//   gate_advance       test the fold, load the full gate's block for the fold's survivors (STAGES >= 1);
+//   gate_finish        test the gate; survivors (~0.04 % of x) go to the queue.
+// STAGES (gate_stages): 0 loads the gate's block first and gate_advance is empty; 1 tests the stage-1 fold first; 2 tests
+// the stage-0 filter before the fold (x1's filter word is loaded by gate_issue_first, and gate_issue_second tests both
+// words and loads the fold's blocks: the filter's trip hides behind x2's arithmetic).  Each stage is a superset of the
+// next, so the queued x are exactly the full gate's survivors in every case.
+// The state between the phases is local to one walk; lanes walk a group in lock-step, so its lane masks live under one
+// exec mask, and nothing is pending when the walk returns.  A block is loaded only in the lanes still in the running
+// (exec-masked) and tested in all of them, the lane mask ANDed in: the common path has no branch, and no wave-wide
+// early-out either (at k = 1 some lane of a wave's 128 x passes the fold in all but ~1e-9 of the steps).
+struct GatePending {
+  Fe x1, x2;               // lazy x (x_out), as the queue holds them
+  uint32_t t1, t2;         // their indices in the group (wave-uniform)
+  uint2 b1, b2;            // the block last loaded for each x (stale where m1 / m2 is off)
+  uint64_t m1, m2;         // lane masks: the lanes whose x has passed every stage tested so far
+};
+// What crosses a phase lives in as few VGPRs as it can: the lane masks in SGPR pairs (opaque, or the compiler keeps the
+// fold's shifted words in VGPRs to AND them into the gate's), and the shift amounts are recomputed from x's word 1 in
+// every phase (from an opaque v_not_b32, or they are kept: 3 VGPRs per x).  With either in VGPRs the pair loop spilled.
+__device__ __forceinline__ uint64_t lane_mask(bool b) {
+  uint64_t m = __builtin_amdgcn_ballot_w64(b);
+  asm volatile("" : "+s"(m));
+  return m;
+}
+__device__ __forceinline__ bool in_mask(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ GateBits gate_bits_again(uint32_t w1, uint32_t s2) {
+  uint32_t n;
+  asm volatile("v_not_b32 %0, %1" : "=v"(n) : "v"(w1));
+  return GateBits{n, n >> 5, n >> s2};
+}
+// Nothing crosses a phase boundary in the scheduler: the field products are non-volatile asm, and without this
+// the loads' first uses (and with them the waits) move up in front of the products meant to cover them.
+__device__ __forceinline__ void gate_fence() { __builtin_amdgcn_sched_barrier(0); }
+
 template <int STAGES>
-__device__ __forceinline__ void gate_pair(const ScanArgs& A, ProbeQueue& Q, const Fe& x1, uint32_t step1, bool has2,
-                                          const Fe& x2, uint32_t step2, uint32_t job) {
-  bool h1, h2;
-  const uint32_t s2 = gate_s2(A);
-  const GateBits b1 = gate_bits(x1.v[1], s2), b2 = gate_bits(x2.v[1], s2);
-  if constexpr (STAGES >= 1) {
-    bool s1 = true, s2p = has2;
-    if constexpr (STAGES == 2) {
-      // stage 0 (L2-resident, one bit per member: ~63 % of x pass at k = 4); the fold's line (read from the MALL at
-      // k = 4) is fetched only for its survivors.  No ballot: with ~63 % passing a wave almost never skips.
-      const uint32_t v1 = A.gate0[x1.v[0] & A.gate0_mask], v2 = A.gate0[x2.v[0] & A.gate0_mask];
-      s1 = (int32_t)shl_mod32(v1, b1.a1) < 0;
-      s2p = has2 && (int32_t)shl_mod32(v2, b2.a1) < 0;
-    }
-    // stage 1 (the fold: L2-resident at k = 1); the full gate's line is fetched only for its survivors
-    uint2 f1, f2;                                  // read only where loaded (s1 / s2p)
-    if (STAGES == 1 || s1) f1 = gate_block(A.gate1, A.gate1_mask, x1);
-    if (STAGES == 1 || s2p) f2 = gate_block(A.gate1, A.gate1_mask, x2);
-    s1 = s1 && gate_block_pass(f1, b1);
-    s2p = s2p && gate_block_pass(f2, b2);
-    if (__ballot(s1 || s2p) == 0) return;
-    uint2 w1, w2;                                  // read only where loaded (s1 / s2p)
-    if (s1) w1 = gate_block(A.gate, A.gate_mask, x1);
-    if (s2p) w2 = gate_block(A.gate, A.gate_mask, x2);
-    h1 = s1 && gate_block_pass(w1, b1);
-    h2 = s2p && gate_block_pass(w2, b2);
+__device__ __forceinline__ void gate_issue_first(const ScanArgs& A, GatePending& G, const Fe& x1, uint32_t t1) {
+  G.x1 = x1;
+  G.t1 = t1;
+  G.m1 = lane_mask(true);
+  if constexpr (STAGES == 2)
+    G.b1 = uint2{A.gate0[x1.v[0] & A.gate0_mask], 0};   // stage 0 (L2-resident, one bit per member: ~63 % of x pass at k = 4)
+  else
+    G.b1 = gate_block(STAGES == 1 ? A.gate1 : A.gate, STAGES == 1 ? A.gate1_mask : A.gate_mask, x1);
+  gate_fence();
+}
+template <int STAGES>
+__device__ __forceinline__ void gate_issue_second(const ScanArgs& A, GatePending& G, bool has2, const Fe& x2,
+                                                  uint32_t t2) {
+  G.x2 = x2;
+  G.t2 = t2;
+  G.m2 = lane_mask(has2);
+  if (!has2) G.b2 = uint2{0, 0};
+  if constexpr (STAGES == 2) {
+    // the fold's line (read from the MALL at k = 4) is fetched only for stage 0's survivors
+    uint32_t v2 = 0;
+    if (has2) v2 = A.gate0[x2.v[0] & A.gate0_mask];
+    gate_fence();
+    G.m1 = lane_mask((int32_t)shl_mod32(G.b1.x, gate_bits_again(G.x1.v[1], 0).a1) < 0);
+    G.m2 = lane_mask(has2 & ((int32_t)shl_mod32(v2, gate_bits_again(x2.v[1], 0).a1) < 0));
+    if (in_mask(G.m1)) G.b1 = gate_block(A.gate1, A.gate1_mask, G.x1);
+    if (in_mask(G.m2)) G.b2 = gate_block(A.gate1, A.gate1_mask, x2);
   } else {
-    const uint2 w1 = gate_block(A.gate, A.gate_mask, x1), w2 = gate_block(A.gate, A.gate_mask, x2);
-    h1 = gate_block_pass(w1, b1);
-    h2 = has2 && gate_block_pass(w2, b2);
+    if (has2) G.b2 = gate_block(STAGES == 1 ? A.gate1 : A.gate, STAGES == 1 ? A.gate1_mask : A.gate_mask, x2);
   }
-  if (__ballot(h1 || h2) == 0) return;
-  q_push(Q, h1, x1, job, step1);
+  gate_fence();
+}
+// stage 1 (the fold: L2-resident at k = 1); the full gate's line is fetched only for its survivors
+template <int STAGES>
+__device__ __forceinline__ void gate_advance(const ScanArgs& A, GatePending& G) {
+  if constexpr (STAGES >= 1) {
+    gate_fence();
+    const uint32_t s2 = gate_s2(A);
+    G.m1 &= lane_mask(gate_block_pass(G.b1, gate_bits_again(G.x1.v[1], s2)));
+    G.m2 &= lane_mask(gate_block_pass(G.b2, gate_bits_again(G.x2.v[1], s2)));
+    if (in_mask(G.m1)) G.b1 = gate_block(A.gate, A.gate_mask, G.x1);
+    if (in_mask(G.m2)) G.b2 = gate_block(A.gate, A.gate_mask, G.x2);
+    gate_fence();
+  }
+}
+template <int STAGES>
+__device__ __forceinline__ void gate_finish(const ScanArgs& A, ProbeQueue& Q, GatePending& G, uint32_t job,
+                                            uint32_t base) {
+  gate_fence();
+  const uint32_t s2 = gate_s2(A);
+  const uint64_t h1 = G.m1 & lane_mask(gate_block_pass(G.b1, gate_bits_again(G.x1.v[1], s2)));
+  const uint64_t h2 = G.m2 & lane_mask(gate_block_pass(G.b2, gate_bits_again(G.x2.v[1], s2)));
+  G.m1 = G.m2 = 0;
+  if ((h1 | h2) == 0) return;
+  q_push(Q, in_mask(h1), G.x1, job, base + G.t1);
   q_drain(A, Q, kDrainAt);
-  q_push(Q, h2, x2, job, step2);
+  q_push(Q, in_mask(h2), G.x2, job, base + G.t2);
   q_drain(A, Q, kDrainAt);
 }
 

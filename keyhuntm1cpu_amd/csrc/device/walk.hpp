@@ -99,7 +99,8 @@ __device__ __forceinline__ Fe fe_small(uint32_t v) {
 // The x-only step, the one copy of its arithmetic for every -m bsgs walk: x1 = x(C - GSn[i]) (pts[511 - i]) and, if
 // PAIR, x2 = x(C + GSn[i]) (pts[513 + i]) from idx = 1 / (GSn[i].x - C.x), C.y, negCx = p - C.x and negCy = p - C.y, so
 // every add is lazy: x = s^2 + nu, nu = nx[i] + negCx riding in the squaring's reduction (fm_sqr_add), s = (GSn.y +/-
-// C.y) * idx.  Out through x_out<XMODE> to sink.one / sink.pair with step = base + the point's index in its group.
+// C.y) * idx.  Out through x_out<XMODE> to the sink with step = base + the point's index in its group: sink.first(x1) as
+// soon as x1 is finished and sink.pair(x1, x2) after x2 (a sink with loads to hide issues x1's in first), or sink.one.
 template <int XMODE>
 __device__ __forceinline__ void x_of_slope(const ScanArgs& A, Fe& x, const Fe& gy, const Fe& cy, const Fe& idx,
                                            const Fe& nu) {
@@ -110,7 +111,7 @@ __device__ __forceinline__ void x_of_slope(const ScanArgs& A, Fe& x, const Fe& g
   x_out<XMODE>(A, x);
 }
 template <int XMODE, bool PAIR, class SINK>
-__device__ __forceinline__ void step_x(const ScanArgs& A, const SINK& sink, const AffPt& C, const Fe& negCx,
+__device__ __forceinline__ void step_x(const ScanArgs& A, SINK& sink, const AffPt& C, const Fe& negCx,
                                        const Fe& negCy, Fe idx, int i, uint32_t base) {
   const GsnTable gsn{A.gsn};
   Fe u, x1, x2;
@@ -118,6 +119,7 @@ __device__ __forceinline__ void step_x(const ScanArgs& A, const SINK& sink, cons
   fm_add_lazy(u, gsn.nx(i), negCx);             // nu = -(C.x + GSn.x)
   x_of_slope<XMODE>(A, x1, g.y, C.y, idx, u);
   if constexpr (PAIR) {
+    sink.first(x1, base + kHalf - 1 - (uint32_t)i);
     x_of_slope<XMODE>(A, x2, g.y, negCy, idx, u);   // GSn.y - C.y
     sink.pair(x1, base + kHalf - 1 - (uint32_t)i, x2, base + kHalf + 1 + (uint32_t)i);
   } else {
@@ -125,26 +127,44 @@ __device__ __forceinline__ void step_x(const ScanArgs& A, const SINK& sink, cons
   }
 }
 
-// The gated walks' sink: each step's two x gate-tested together (x2 absent at step 511).
+// The gated walks' sink: each step's two x gate-tested together (x2 absent at step 511), in the phases of
+// probe_queue.hpp.  first / pair issue the step's first loads and leave it pending; the walk calls advance and finish
+// behind the next step's products; one (step 511) leaves its single x pending in the same way, so every advance and
+// finish of the walk has a step to work on and the loop carries no flag.  t = the point's index in its group (step_x
+// is given base 0, so t stays wave-uniform; base is added when a survivor is queued).
 template <int STAGES>
 struct GateSink {
   const ScanArgs& A;
   ProbeQueue& Q;
-  uint32_t job;
-  __device__ __forceinline__ void pair(const Fe& x1, uint32_t step1, const Fe& x2, uint32_t step2) const {
-    gate_pair<STAGES>(A, Q, x1, step1, true, x2, step2, job);
+  uint32_t job, base;
+  GatePending G;
+  __device__ __forceinline__ void first(const Fe& x1, uint32_t t1) { gate_issue_first<STAGES>(A, G, x1, t1); }
+  __device__ __forceinline__ void pair(const Fe&, uint32_t, const Fe& x2, uint32_t t2) {
+    gate_issue_second<STAGES>(A, G, true, x2, t2);
   }
-  __device__ __forceinline__ void one(const Fe& x1, uint32_t step1) const {
-    gate_pair<STAGES>(A, Q, x1, step1, false, x1, 0, job);
+  __device__ __forceinline__ void advance() { gate_advance<STAGES>(A, G); }
+  __device__ __forceinline__ void finish() { gate_finish<STAGES>(A, Q, G, job, base); }
+  __device__ __forceinline__ void one(const Fe& x1, uint32_t t1) {
+    gate_issue_first<STAGES>(A, G, x1, t1);
+    gate_issue_second<STAGES>(A, G, false, x1, 0);
   }
 };
 
 // The walk of kScanG* (-m bsgs with a level-0 gate), the product path: the reference's points in its backward order
 // (keyhunt.cpp:3873-3943), x only, given inv = 1 / prod_{i<512} (GSn[i].x - C.x) and the forward prefix products
-// P_i = prod_{k<=i} dx_k in scr (stride lanes).  For i = 511 ... 0: idx = inv * P_{i-1}, inv *= dx_i, step_x.  A later
-// step's prefix is loaded right after the prefix register's last use (its HBM latency hides behind a whole step); the
-// first step is peeled and the loop's prefix load is unconditional, so the loop body issues the same vector-memory
-// sequence every time and the waitcnt pass waits for exactly the operand it needs.
+// P_i = prod_{k<=i} dx_k in scr (stride lanes).  For i = 511 ... 0: idx = inv * P_{i-1}, inv *= dx_i, step_x.
+// The gate's two dependent round trips hide behind the next step's products: step_x leaves its step pending in the sink
+// with the fold loads issued (x1's ahead of x2's arithmetic); the next step's first product (idx = inv * pre, or the
+// odd step's rebuild pre * dx) runs, sink.advance tests the folds and issues the full-gate loads, the next product
+// runs, and sink.finish tests the gate and queues its survivors.  Step 511 is finished by the loop's first pass, step 1
+// ahead of step 0 (idx = inv: no product to hide behind) and step 0 ahead of the centre's probe: nothing is pending
+// on return.
+// A later step's prefix is loaded behind finish, a step (the half stream: two) ahead of its use, so its HBM latency
+// hides behind a whole step and finish never has a prefetch to wait for; issued in front of the second overlapped
+// product it held 8 more VGPRs through it (spills on the hot path, whose reloads waited for the gate loads at once).
+// The first step is peeled and the loop's prefix load is unconditional (the half stream's last pair reloads P_1 for
+// nothing), so the loop body issues the same vector-memory sequence every time and the waitcnt pass waits for exactly
+// the operand it needs.
 // Full stream (HALF = false): every P_i is stored; step i reads P_{i-1} and loads P_{i-2}.  Half stream
 // (KHB_HALF_STREAM): only the odd P_1 ... P_509 are stored.  After the peeled step 511 the walk goes in pairs (even i,
 // odd i - 1): the even step needs P_{i-1}, stored, and then loads P_{i-3}; the odd step rebuilds P_{i-2} = P_{i-3} *
@@ -156,7 +176,7 @@ __device__ __forceinline__ void walk_gated(const ScanArgs& A, ProbeQueue& Q, con
   const size_t S = A.stride;
   const GsnTable gsn{A.gsn};
   const uint32_t base = j * KHB_GROUP;
-  const GateSink<STAGES> sink{A, Q, job};
+  GateSink<STAGES> sink{A, Q, job, base};
   // the centre enters as p - C.x and p - C.y, so every per-step add/sub is a lazy add
   Fe negCx, negCy;
   fm_sub(negCx, fe_p(), C.x);
@@ -174,41 +194,54 @@ __device__ __forceinline__ void walk_gated(const ScanArgs& A, ProbeQueue& Q, con
   }
   fm_add_lazy(dx, gsn.x(kHalf - 1), negCx);
   fm_mul(inv, inv, dx);
-  step_x<kScanG, false>(A, sink, C, negCx, negCy, idx, kHalf - 1, base);
+  step_x<kScanG, false>(A, sink, C, negCx, negCy, idx, kHalf - 1, 0);
   if constexpr (HALF) {
     // pairs (even i, odd i - 1), i = 510 ... 2; pre = P_{i-1} on entry
     for (int i = (int)kHalf - 2; i >= 2; i -= 2) {
       fm_mul(idx, inv, pre);                                 // even step i: P_{i-1} (odd index, stored)
-      if (i > 2) pre = scr_ld(scr + (size_t)(i - 3) * S);    // P_{i-3} for step i - 1 (and i - 2)
+      sink.advance();                                        // step i + 1's folds; its gate loads
       fm_add_lazy(dx, gsn.x(i), negCx);
       fm_mul(inv, inv, dx);
-      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i, base);
+      sink.finish();
+      pre = scr_ld(scr + (size_t)(i > 2 ? i - 3 : 1) * S);   // P_{i-3} for step i - 1 (and i - 2); i = 2: unused
+      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i, 0);
       // odd step i - 1: P_{i-2} = P_{i-3} * dx_{i-2} (i - 1 = 1: P_0 = dx_0)
       fm_add_lazy(dx, gsn.x(i - 2), negCx);
       if (i > 2) {
         fm_mul(idx, pre, dx);
+        sink.advance();                                      // step i's
         fm_mul(idx, inv, idx);
       } else {
+        sink.advance();
         fm_mul(idx, inv, dx);
       }
+      sink.finish();
       fm_add_lazy(dx, gsn.x(i - 1), negCx);
       fm_mul(inv, inv, dx);
-      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i - 1, base);
+      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i - 1, 0);
     }
-    step_x<kScanG, true>(A, sink, C, negCx, negCy, inv, 0, base);     // step 0: idx = inv
+    sink.advance();                                                // step 1's, ahead of step 0 (idx = inv: no product)
+    sink.finish();
+    step_x<kScanG, true>(A, sink, C, negCx, negCy, inv, 0, 0);
   } else {
     for (int i = (int)kHalf - 2; i >= 0; --i) {
       if (i > 0) {
         fm_mul(idx, inv, pre);
-        pre = scr_ld(scr + (size_t)(i >= 2 ? i - 2 : 0) * S);   // i = 1: a harmless reload of prefix 0
+        sink.advance();                                         // step i + 1's folds; its gate loads
         fm_add_lazy(dx, gsn.x(i), negCx);
         fm_mul(inv, inv, dx);
+        sink.finish();
+        pre = scr_ld(scr + (size_t)(i >= 2 ? i - 2 : 0) * S);   // i = 1: a harmless reload of prefix 0
       } else {
+        sink.advance();
+        sink.finish();
         idx = inv;
       }
-      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i, base);
+      step_x<kScanG, true>(A, sink, C, negCx, negCy, idx, i, 0);
     }
   }
+  sink.advance();                                // step 0's: nothing is pending past here
+  sink.finish();
   probe<false>(A, Q, C.x, job, j, kHalf);        // the centre, pts[512]
 }
 
@@ -230,6 +263,7 @@ struct ProbeSink {
   const ScanArgs& A;
   ProbeQueue& Q;
   uint32_t job, j;
+  __device__ __forceinline__ void first(const Fe&, uint32_t) const {}
   __device__ __forceinline__ void pair(const Fe& x1, uint32_t t1, const Fe& x2, uint32_t t2) const {
     if constexpr (MODE == kScan)            // both x before either probe load is issued
       asm volatile("" ::"v"(x1.v[0]), "v"(x2.v[0]), "v"(x1.v[7]), "v"(x2.v[7]) : "memory");
@@ -343,6 +377,7 @@ template <int MODE>
 struct XPointSink {
   const ScanArgs& A;
   uint32_t job, j;
+  __device__ __forceinline__ void first(const Fe&, uint32_t) const {}
   __device__ __forceinline__ void pair(const Fe& x1, uint32_t t1, const Fe& x2, uint32_t t2) const {
     // both x before either bloom load is issued
     asm volatile("" ::"v"(x1.v[3]), "v"(x2.v[3]), "v"(x1.v[7]), "v"(x2.v[7]) : "memory");

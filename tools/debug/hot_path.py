@@ -18,7 +18,9 @@ count of `s_cmp_eq_u64` on the path is the number of field products (13 in the p
 Usage: python tools/debug/hot_path.py file.s <kernel-substring> <header-label> [-v]
 Prints the instruction classes of tools/debug/bb_path.py (full-rate, half-rate, cndmask, nop), the carry adds,
 the moves by source and the spill ops and, with -v, every opcode count and each cndmask with the instruction
-before it."""
+before it.  With -w, every vector-memory, LDS and scratch instruction and every s_waitcnt on the path, in path order,
+each with the number of VALU instructions and of v_mad_u64_u32 (64 per field product, 36 per squaring) issued on
+the path before it: where the loads are issued and where the walk waits for them."""
 import re
 import sys
 from collections import Counter
@@ -40,6 +42,7 @@ def main():
     ops, cnd, seen = Counter(), [], 0
     prev = ""
     movs, zero, inner = Counter(), set(), set()
+    mem, nvalu = [], 0
 
     def track(s):
         """Keep `zero` (VGPRs known to hold 0) current over instruction s; classify s if it is a move."""
@@ -90,6 +93,9 @@ def main():
             continue
         if op.startswith("s_cbranch"):
             continue
+        if op.startswith(("global_", "flat_", "buffer_", "scratch_", "ds_", "s_waitcnt")):
+            mem.append((nvalu, ops["v_mad_u64_u32"], s))
+        nvalu += op.startswith("v_")
         ops[op] += 1
         k = track(s)
         if k:
@@ -106,6 +112,9 @@ def main():
     print("carry adds", sum(n for o, n in ops.items() if o.startswith(("v_addc_co_u32", "v_add_co_u32"))),
           "v_mov_b32", sum(movs.values()), dict(movs),
           "spill ops", sum(n for o, n in ops.items() if o.startswith("scratch_")))
+    if "-w" in sys.argv:
+        for v, m, t in mem:
+            print(f"  valu {v:5d} mad {m:4d}  {t}")
     if "-v" in sys.argv:
         for k, v in ops.most_common(40):
             print(f"  {v:5d} {k}")

@@ -9,7 +9,7 @@
 #   3. config E: bench.py --workload address, and SQ_INSTS_VALU of one 8-chunk launch of the product
 #      library and, where a hash-less addrwalk build is present (its patcher went in round 8, when it no longer
 #      applied; git history has it), of that build (the x/y walk term of the floor, tools/addr_floor.py).
-# Usage: bash tools/gpu/round_profile.sh <tag> [steps]     Env: PARTS (default "trace pmc address"), PMC_JOBS
+# Usage: bash tools/gpu/round_profile.sh <tag> [steps]     Env: LIB, PARTS (default "trace pmc address"), PMC_JOBS
 # (chunks per PMC launch, default 4096 = the bench's auto batch at 4 waves/SIMD), K (default 1; K=4 PMC_JOBS=16384
 # PARTS=pmc gives config C's record, profiles/pmc_latest_k4.json).
 set -o pipefail
@@ -18,7 +18,7 @@ TAG=${1:-prof}
 STEPS=${2:-20}
 O=gpurun_out/$TAG
 mkdir -p $O
-L=keyhuntm1cpu_amd/lib/libkhbsgs.so
+L=${LIB:-keyhuntm1cpu_amd/lib/libkhbsgs.so}      # LIB=<other libkhbsgs.so>: the PMC passes of an A/B's other side
 W=keyhuntm1cpu_amd/lib/variants/libkhbsgs_addrwalk.so
 J=${PMC_JOBS:-4096}
 export K=${K:-1}          # the geometry's k (perf_variants reads K; K=4 with PMC_JOBS=16384 is config C's launch)
