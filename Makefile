@@ -15,14 +15,15 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wno-unused-result -Wno-
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -march=x86-64-v3 -Wall -Wextra -Wno-unused-function -Wno-unused-parameter -Wno-unknown-pragmas -pthread
 
 DEV_HDRS  := $(wildcard $(CSRC)/device/*.hpp) $(CSRC)/scan_kernels.hpp $(CSRC)/abi.hpp include/khbsgs.h
-# libkhbsgs: the C ABI by concern (khbsgs, khb_tables, khb_selftest, k_check, k_mini; abi.hpp) + one translation unit per
+# libkhbsgs: the C ABI by concern (khbsgs, khb_tables, khb_selftest, k_check, k_mini, k_kang; abi.hpp) + one translation unit per
 # group of k_giant_scan instances, so `make -j` compiles the heavy kernels in parallel
-HIP_SRCS  := $(CSRC)/khbsgs.hip $(CSRC)/khb_tables.hip $(CSRC)/khb_selftest.hip $(CSRC)/k_bsgs.hip $(CSRC)/k_addr.hip $(CSRC)/k_addr_e.hip $(CSRC)/k_addr_eth.hip $(CSRC)/k_addr_x.hip $(CSRC)/k_vanity.hip $(CSRC)/k_mini.hip $(CSRC)/k_baby.hip \
+HIP_SRCS  := $(CSRC)/khbsgs.hip $(CSRC)/khb_tables.hip $(CSRC)/khb_selftest.hip $(CSRC)/k_bsgs.hip $(CSRC)/k_addr.hip $(CSRC)/k_addr_e.hip $(CSRC)/k_addr_eth.hip $(CSRC)/k_addr_x.hip $(CSRC)/k_vanity.hip $(CSRC)/k_mini.hip $(CSRC)/k_kang.hip $(CSRC)/k_baby.hip \
              $(CSRC)/k_check.hip
 HIP_OBJS  := $(patsubst $(CSRC)/%.hip,build/hip/%.o,$(HIP_SRCS))
 HOST_SRCS := $(CSRC)/host/u256.cpp $(CSRC)/host/secp_host.cpp $(CSRC)/host/bloom_host.cpp \
              $(CSRC)/host/bsgs_host.cpp $(CSRC)/host/bsgs_files.cpp $(CSRC)/host/engine.cpp \
-             $(CSRC)/host/address_host.cpp $(CSRC)/host/vanity_host.cpp $(CSRC)/host/mini_host.cpp $(CSRC)/host/mini_table.cpp
+             $(CSRC)/host/address_host.cpp $(CSRC)/host/vanity_host.cpp $(CSRC)/host/mini_host.cpp $(CSRC)/host/mini_table.cpp \
+             $(CSRC)/host/kang_host.cpp
 HOST_HDRS := $(wildcard $(CSRC)/host/*.hpp) $(DEV_HDRS) include/khhost.h
 HOST_OBJS := $(patsubst $(CSRC)/host/%.cpp,build/host/%.o,$(HOST_SRCS))
 

@@ -402,6 +402,54 @@ int khb_mini_filter(khb_ctx* ctx, const uint8_t* first_digits, uint64_t count, c
  * khb_load_mini_table. */
 int khb_mini_pubkey(khb_ctx* ctx, const uint8_t* scalars_be, uint8_t* xy_out, uint8_t* flags_out, uint32_t n);
 
+/* ---- Pollard's kangaroo walk with distinguished points (no reference counterpart) ----
+ * The interval search for one public key where the interval outgrows any BSGS table: a herd of kangaroos walks the
+ * curve, each with its point and the distance it has travelled, and reports the distinguished points it lands on.
+ * The host (libkhhost: khh_kang_*) owns the algorithm around it: tame kangaroos (even index) start at d*G, wild ones
+ * (odd index) at Q + d*G, and a tame and a wild one meeting at a distinguished point give the key.  The library only
+ * walks: kangaroo i at canonical (x, y) with distance d takes jump j = x mod 32, or (j + 1) mod 32 when x == J_j.x,
+ * and becomes (x, y) + J_j with d + s_j (a plain 256-bit add).  The new point is distinguished iff bits 32 ..
+ * 32 + dp_bits - 1 of x are zero (dp_bits = 0: every point), and {i, x, d} is then appended to the launch's ring.
+ * The herd's state stays on the device from launch to launch.  Launches, stores and reads of one context are ordered
+ * on one stream; two launches may be in flight (two rings alternate, FIFO collect), a third returns KHB_EBUSY.
+ * Additions to ABI 7, as the -m minikeys calls were: the version stays 7; a caller checks for the khb_kang_submit
+ * symbol. */
+typedef struct {
+  uint32_t kangaroo;        /* index in the herd */
+  uint8_t x_be[32];         /* the distinguished point's x */
+  uint8_t dist_be[32];      /* the kangaroo's distance at that point */
+} khb_kang_dp;
+typedef struct {
+  uint64_t steps_walked;    /* jumps made, counted on the device (herd x steps) */
+  uint64_t n_dp;            /* distinguished points met (counted past the ring's capacity) */
+  uint64_t second_choice;   /* times the x == J_j.x rule chose jump (j + 1) mod 32 */
+  uint32_t dp_overflow;     /* 1: n_dp > the ring's capacity, the rest were not kept (the walk itself is unaffected) */
+  float kernel_ms;          /* the walk kernel, by HIP events; -1 if unavailable */
+} khb_kang_stats;
+/* Kangaroo slots per lane (a build-time constant): a lane shares one field inversion among this many jumps; kangaroo
+ * i is slot i mod khb_kang_per_lane() of lane i / khb_kang_per_lane(). */
+uint32_t khb_kang_per_lane(void);
+/* The herd of one full residency of the walk kernel on `device` (0 if the device is unusable). */
+uint32_t khb_kang_full_herd(int device);
+/* The 32 jumps: dist_be[32 j ..] = s_j (32 bytes BE), xy_be[64 j ..] = J_j = s_j * G.  KHB_EINVAL when two J_j.x are
+ * equal (the step rule's second choice needs them distinct); the table loaded before stays. */
+int khb_kang_load_jumps(khb_ctx* ctx, const uint8_t* dist_be, const uint8_t* xy_be);
+/* Kangaroos first .. first + n - 1 of the herd: points x||y BE (on the curve, not infinity) and distances (32 bytes
+ * BE).  first <= the herd's size (KHB_EINVAL otherwise): a store past the end grows the herd, any other replaces
+ * kangaroos; n = 0 with first = 0 forgets the herd.  Ordered behind the launches in flight. */
+int khb_kang_store(khb_ctx* ctx, uint32_t first, uint32_t n, const uint8_t* xy_be, const uint8_t* dist_be);
+int khb_kang_read(khb_ctx* ctx, uint32_t first, uint32_t n, uint8_t* xy_be, uint8_t* dist_be);
+uint32_t khb_kang_herd(const khb_ctx* ctx);
+/* Every kangaroo of the herd makes `steps` jumps.  KHB_EINVAL, and nothing is launched, without jumps or a herd,
+ * for steps == 0 and for dp_bits > 32. */
+int khb_kang_submit(khb_ctx* ctx, uint32_t steps, uint32_t dp_bits);
+/* Wait for the OLDEST launch in flight and retire it; up to cap of its distinguished points (unordered).
+ * KHB_EINCOMPLETE: the device's count of jumps differs from herd x steps. */
+int khb_kang_collect(khb_ctx* ctx, khb_kang_dp* out, uint32_t cap, khb_kang_stats* stats);
+/* Ring entries of later launches (default 2^18); small values are for tests of the caller's overflow path. */
+int khb_kang_set_ring_capacity(khb_ctx* ctx, uint32_t cap);
+uint32_t khb_kang_ring_capacity(const khb_ctx* ctx);
+
 /* ---- baby-step tables on the GPU (thread_bPload, keyhunt.cpp:4404-4592; orchestration 1615-1880) ----
  * Uses the loaded giant table as Gn[i] = (i+1)*G, _2Gn = 1024*G and the lane offsets for jobs of
  * groups_per_job groups.  Job k covers baby steps ic = k*groups_per_job*1024 + [0, groups_per_job*1024)

@@ -27,8 +27,9 @@ extern "C" {
  * ABI 10 added -m vanity: khh_addr_new_vanity, khh_addr_vanity_intervals, khh_addr_vanity_match and
  * khh_vanity_target_ok.
  * ABI 11 added -m minikeys: khh_mini_new / khh_mini_free, khh_mini_search, khh_mini_string, khh_mini_valid,
- * khh_mini_key, khh_mini_table and khh_mini_set_queue_capacity / khh_mini_set_hit_capacity. */
-#define KHH_ABI_VERSION 11
+ * khh_mini_key, khh_mini_table and khh_mini_set_queue_capacity / khh_mini_set_hit_capacity.
+ * ABI 12 added the kangaroo interval search: the khh_kang_* calls. */
+#define KHH_ABI_VERSION 12
 int khh_abi_version(void);
 
 typedef struct khh_tables khh_tables;
@@ -319,6 +320,48 @@ int khh_mini_search(const khh_mini* m, const char* first22, size_t first_len, ui
                     int n_devices, uint32_t lanes, uint64_t per_launch, char* minikeys, uint8_t* keys_be, uint8_t* rmd,
                     uint32_t cap, uint32_t* n_found, uint64_t* stats_out, uint32_t stats_len, char* err,
                     size_t errlen);
+
+/* ---- Pollard's kangaroo interval search for one public key (no reference counterpart) ----
+ * The key of pub_xy is sought in [start, end), W = end - start with 2^16 <= W <= 2^200 (NULL with err otherwise, or
+ * when end exceeds the group order).  Kangaroo i is tame for even i (its point is d*G) and wild for odd i (Q + d*G,
+ * Q = P - start*G); all jump by the 32 jumps (s_j, s_j*G) of the handle, s_j drawn from the seeded generator in
+ * [1, 2^(ceil(w/2) + 1)), w the bit length of W, redrawn until the 32 x differ.  The step rule and the distinguished
+ * points are include/khbsgs.h's.  A tame and a wild kangaroo on one distinguished x give the key, which is verified
+ * (key*G == P) before it is reported; two of one kind have merged, and the later one is replaced and counted.
+ * dp_bits < 0 and herd == 0 ask for the defaults: the largest herd (kangaroos per device) and dp_bits with
+ * herd * 2^dp_bits <= 2^(floor(w/2) - 2), the herd at most herd_cap (0 = one full residency of the walk kernel times
+ * its slots per lane). */
+typedef struct khh_kang khh_kang;
+khh_kang* khh_kang_new(const uint8_t pub_xy[64], const uint8_t start_be[32], const uint8_t end_be[32], int dp_bits,
+                       uint64_t herd, uint64_t seed, uint64_t herd_cap, char* err, size_t errlen);
+void khh_kang_free(khh_kang* k);
+int khh_kang_params(const khh_kang* k, uint32_t* dp_bits, uint64_t* herd, uint32_t* width_bits);
+/* The jumps as khb_kang_load_jumps takes them: 32 distances (32 bytes BE) and 32 points (x||y BE). */
+int khh_kang_jumps(const khh_kang* k, uint8_t* dist_be, uint8_t* xy);
+/* The first n kangaroos a search gives its device number `stream` (0 for the first), by the host's own k*G. */
+int khh_kang_make_herd(const khh_kang* k, uint32_t stream, uint64_t n, uint8_t* xy, uint8_t* dist_be);
+/* The step rule on the portable field of device/fe.hpp, so the host logic is testable without a GPU: the n kangaroos
+ * (x||y BE, distances 32 bytes BE, updated in place) make `steps` jumps each.  The distinguished points come step by
+ * step, ascending kangaroo within a step: up to cap of them in dp_kangaroo / dp_x_be / dp_dist_be (any may be NULL),
+ * *n_dp counts them all, *second_choice the times the x == J_j.x rule fired. */
+int khh_kang_cpu_walk(const khh_kang* k, uint8_t* xy, uint8_t* dist_be, uint64_t n, uint32_t steps, uint32_t dp_bits,
+                      uint32_t* dp_kangaroo, uint8_t* dp_x_be, uint8_t* dp_dist_be, uint64_t cap, uint64_t* n_dp,
+                      uint64_t* second_choice);
+/* Tests: ring entries per launch (0 = sized from the herd); the first n kangaroos of the first device's herd; keep
+ * that device's herd as the search leaves it, for khh_kang_final_herd (*n = its size, up to cap copied). */
+int khh_kang_set_ring_capacity(khh_kang* k, uint32_t cap);
+int khh_kang_plant(khh_kang* k, const uint8_t* xy, const uint8_t* dist_be, uint64_t n);
+int khh_kang_keep_herd(khh_kang* k, int keep);
+int khh_kang_final_herd(const khh_kang* k, uint8_t* xy, uint8_t* dist_be, uint64_t cap, uint64_t* n);
+/* One host thread and one herd per device, one shared table of distinguished points that grows and is never
+ * truncated.  n_devices == 0: one herd walks on the CPU through khh_kang_cpu_walk's code.  max_steps: jumps in all
+ * (0 = no limit); reaching it leaves *found = 0 and is no error.  After a launch whose ring overflowed the launches
+ * are halved; the lost points cost time, not correctness, and are counted.  stats_out[0 .. stats_len) of
+ * KHH_KANG_STATS values: steps, distinguished points digested, dead (merged kangaroos replaced), lost points,
+ * launches, microseconds. */
+#define KHH_KANG_STATS 6
+int khh_kang_search(khh_kang* k, const int* devices, int n_devices, uint64_t max_steps, uint8_t key_be[32],
+                    int* found, uint64_t* stats_out, uint32_t stats_len, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 //   khb_selftest.hip  field / probe / hash160 self-tests and the point dumps
 //   k_check.hip       the second / third check: its kernel, tables and khb_check
 //   k_mini.hip        -m minikeys: its kernels, table, launch state and the khb_mini_* calls
+//   k_kang.hip        the kangaroo walk: its kernels, herd state, rings and the khb_kang_* calls
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@ namespace khbk {
 struct CheckIn;                        // k_check.hip
 struct CheckOut;
 struct MiniState;                      // k_mini.hip
+struct KangState;                      // k_kang.hip
 }  // namespace khbk
 
 // One submission's device state.  A context owns two (KHB_QUEUE_DEPTH): khb_submit fills the next
@@ -113,6 +115,8 @@ struct khb_ctx {
   // the targets on the device (d_ck_targets) as the caller passed them: a khb_check with the same bytes
   // uploads only its CheckIn records (no O(n_targets) conversion and upload per batch)
   std::vector<uint8_t> ck_targets_be;
+  // the kangaroo walk (k_kang.hip): jump table, herd state, rings and a stream of its own, allocated on first use
+  khbk::KangState* kang = nullptr;
 };
 
 #pragma GCC visibility push(hidden)    // the library exports the khb_* of include/khbsgs.h only
@@ -211,6 +215,8 @@ ScanArgs make_args(khb_ctx* c, const Slot& S, uint32_t n_jobs, uint32_t group_be
                    uint32_t per_item = 0);
 // Defined in k_mini.hip: frees the context's -m minikeys state (khb_close).
 void mini_free(khb_ctx* c);
+// Defined in k_kang.hip: frees the context's kangaroo state (khb_close).
+void kang_free(khb_ctx* c);
 
 }  // namespace khbk
 #pragma GCC visibility pop

@@ -10,6 +10,7 @@
 #include "address_host.hpp"
 #include "bsgs_host.hpp"
 #include "engine.hpp"
+#include "kang_host.hpp"
 #include "mini_host.hpp"
 
 using namespace khb;
@@ -30,6 +31,10 @@ struct khh_addr {
 struct khh_mini {
   MiniSearch S;
   uint32_t queue_cap = 0, hit_cap = 0;   // tests: the launches' capacities (0 = library defaults)
+};
+
+struct khh_kang {
+  KangSearch S;
 };
 
 static void set_err(char* err, size_t n, const std::string& m) {
@@ -665,6 +670,131 @@ int khh_mini_search(const khh_mini* m, const char* first22, size_t first_len, ui
     const uint64_t v[KHH_MINI_STATS] = {st.candidates, st.valid, st.bad_keys, st.hits, st.launches, st.rescans,
                                         (uint64_t)(st.filter_seconds * 1e6), (uint64_t)(st.keys_seconds * 1e6)};
     memcpy(stats_out, v, sizeof(uint64_t) * (stats_len < KHH_MINI_STATS ? stats_len : KHH_MINI_STATS));
+  }
+  if (rc) set_err(err, errlen, e);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------- kangaroo interval search
+khh_kang* khh_kang_new(const uint8_t pub_xy[64], const uint8_t start_be[32], const uint8_t end_be[32], int dp_bits,
+                       uint64_t herd, uint64_t seed, uint64_t herd_cap, char* err, size_t errlen) {
+  if (!pub_xy || !start_be || !end_be) {
+    set_err(err, errlen, "no public key or interval");
+    return nullptr;
+  }
+  if (herd_cap == 0) {
+    herd_cap = khb_kang_full_herd(0);
+    if (herd_cap == 0) herd_cap = (uint64_t)khb_kang_per_lane() << 18;      // an MI355X's 262,144 lanes
+  }
+  khh_kang* k = new khh_kang();
+  std::string e;
+  if (!kang_init(k->S, pt_from_be(pub_xy), U256::from_be(start_be), U256::from_be(end_be), dp_bits, herd, seed,
+                 herd_cap, &e)) {
+    set_err(err, errlen, e);
+    delete k;
+    return nullptr;
+  }
+  return k;
+}
+
+void khh_kang_free(khh_kang* k) { delete k; }
+
+int khh_kang_params(const khh_kang* k, uint32_t* dp_bits, uint64_t* herd, uint32_t* width_bits) {
+  if (!k) return KHB_EINVAL;
+  if (dp_bits) *dp_bits = k->S.dp_bits;
+  if (herd) *herd = k->S.herd;
+  if (width_bits) *width_bits = (uint32_t)k->S.w_bits;
+  return KHB_OK;
+}
+
+int khh_kang_jumps(const khh_kang* k, uint8_t* dist_be, uint8_t* xy) {
+  if (!k || !dist_be || !xy) return KHB_EINVAL;
+  for (int j = 0; j < kKangJumps; ++j) {
+    k->S.jump_s[j].to_be(dist_be + 32 * j);
+    pt_to_be(xy + 64 * j, k->S.jump_p[j]);
+  }
+  return KHB_OK;
+}
+
+static void roos_to_be(const KangRoo* r, uint64_t n, uint8_t* xy, uint8_t* dist_be) {
+  for (uint64_t i = 0; i < n; ++i) {
+    pt_to_be(xy + 64 * i, r[i].p);
+    r[i].d.to_be(dist_be + 32 * i);
+  }
+}
+
+static std::vector<KangRoo> roos_from_be(const uint8_t* xy, const uint8_t* dist_be, uint64_t n) {
+  std::vector<KangRoo> r(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    r[i].p = pt_from_be(xy + 64 * i);
+    r[i].d = U256::from_be(dist_be + 32 * i);
+  }
+  return r;
+}
+
+int khh_kang_make_herd(const khh_kang* k, uint32_t stream, uint64_t n, uint8_t* xy, uint8_t* dist_be) {
+  if (!k || !xy || !dist_be) return KHB_EINVAL;
+  for (uint64_t i = 0; i < n; ++i) {
+    const KangRoo r = kang_make(k->S, stream, i, 0);
+    roos_to_be(&r, 1, xy + 64 * i, dist_be + 32 * i);
+  }
+  return KHB_OK;
+}
+
+int khh_kang_cpu_walk(const khh_kang* k, uint8_t* xy, uint8_t* dist_be, uint64_t n, uint32_t steps, uint32_t dp_bits,
+                      uint32_t* dp_kangaroo, uint8_t* dp_x_be, uint8_t* dp_dist_be, uint64_t cap, uint64_t* n_dp,
+                      uint64_t* second_choice) {
+  if (!k || !xy || !dist_be || n == 0 || steps == 0 || dp_bits > 32) return KHB_EINVAL;
+  std::vector<KangRoo> herd = roos_from_be(xy, dist_be, n);
+  std::vector<KangDp> dps;
+  kang_cpu_walk(k->S, herd.data(), n, steps, dp_bits, dps, second_choice);
+  roos_to_be(herd.data(), n, xy, dist_be);
+  if (n_dp) *n_dp = dps.size();
+  for (uint64_t i = 0; i < dps.size() && i < cap; ++i) {
+    if (dp_kangaroo) dp_kangaroo[i] = dps[i].i;
+    if (dp_x_be) dps[i].x.to_be(dp_x_be + 32 * i);
+    if (dp_dist_be) dps[i].d.to_be(dp_dist_be + 32 * i);
+  }
+  return KHB_OK;
+}
+
+int khh_kang_set_ring_capacity(khh_kang* k, uint32_t cap) {
+  if (!k) return KHB_EINVAL;
+  k->S.ring_cap = cap;
+  return KHB_OK;
+}
+
+int khh_kang_plant(khh_kang* k, const uint8_t* xy, const uint8_t* dist_be, uint64_t n) {
+  if (!k || (n && (!xy || !dist_be)) || n > k->S.herd) return KHB_EINVAL;
+  k->S.planted = roos_from_be(xy, dist_be, n);
+  return KHB_OK;
+}
+
+int khh_kang_keep_herd(khh_kang* k, int keep) {
+  if (!k) return KHB_EINVAL;
+  k->S.keep_herd = keep != 0;
+  return KHB_OK;
+}
+
+int khh_kang_final_herd(const khh_kang* k, uint8_t* xy, uint8_t* dist_be, uint64_t cap, uint64_t* n) {
+  if (!k || !n) return KHB_EINVAL;
+  *n = k->S.final_herd.size();
+  if (xy && dist_be) roos_to_be(k->S.final_herd.data(), *n < cap ? *n : cap, xy, dist_be);
+  return KHB_OK;
+}
+
+int khh_kang_search(khh_kang* k, const int* devices, int n_devices, uint64_t max_steps, uint8_t key_be[32],
+                    int* found, uint64_t* stats_out, uint32_t stats_len, char* err, size_t errlen) {
+  if (!k || !found || (n_devices > 0 && !devices)) return KHB_EINVAL;
+  std::vector<int> devs(devices, devices + (n_devices > 0 ? n_devices : 0));
+  KangResult R;
+  std::string e;
+  const int rc = kang_search(k->S, devs, max_steps, R, &e);
+  *found = R.found ? 1 : 0;
+  if (R.found && key_be) R.key.to_be(key_be);
+  if (stats_out) {
+    const uint64_t v[KHH_KANG_STATS] = {R.steps, R.dps, R.dead, R.lost_dps, R.launches, (uint64_t)(R.seconds * 1e6)};
+    memcpy(stats_out, v, sizeof(uint64_t) * (stats_len < KHH_KANG_STATS ? stats_len : KHH_KANG_STATS));
   }
   if (rc) set_err(err, errlen, e);
   return rc;

@@ -511,6 +511,7 @@ int khb_close(khb_ctx* c) {
   hipFree(c->d_abloom);
   hipFree(c->d_van);
   mini_free(c);
+  kang_free(c);
   delete c;
   return KHB_OK;
 }

@@ -67,6 +67,15 @@ class MiniStats(C.Structure):      # khb_mini_stats
                 ("keys_ms", C.c_float)]
 
 
+class KangDp(C.Structure):         # khb_kang_dp
+    _fields_ = [("kangaroo", C.c_uint32), ("x_be", C.c_uint8 * 32), ("dist_be", C.c_uint8 * 32)]
+
+
+class KangStats(C.Structure):      # khb_kang_stats
+    _fields_ = [("steps_walked", C.c_uint64), ("n_dp", C.c_uint64), ("second_choice", C.c_uint64),
+                ("dp_overflow", C.c_uint32), ("kernel_ms", C.c_float)]
+
+
 MINI_ALPHABET = b"123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"   # the reference's Ccoinbuffer_default
 
 _libs: dict[str, C.CDLL] = {}
@@ -171,6 +180,21 @@ def lib(path: str | None = None) -> C.CDLL:
             L.khb_mini_filter.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, P(C.c_uint64), C.c_uint32,
                                           P(C.c_uint64)]
             L.khb_mini_pubkey.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]
+        if hasattr(L, "khb_kang_submit"):        # the kangaroo additions to ABI 7
+            L.khb_kang_per_lane.restype = C.c_uint32
+            L.khb_kang_per_lane.argtypes = []
+            L.khb_kang_full_herd.restype = C.c_uint32
+            L.khb_kang_full_herd.argtypes = [C.c_int]
+            L.khb_kang_load_jumps.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+            L.khb_kang_store.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p]
+            L.khb_kang_read.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p]
+            L.khb_kang_herd.restype = C.c_uint32
+            L.khb_kang_herd.argtypes = [C.c_void_p]
+            L.khb_kang_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+            L.khb_kang_collect.argtypes = [C.c_void_p, P(KangDp), C.c_uint32, P(KangStats)]
+            L.khb_kang_set_ring_capacity.argtypes = [C.c_void_p, C.c_uint32]
+            L.khb_kang_ring_capacity.restype = C.c_uint32
+            L.khb_kang_ring_capacity.argtypes = [C.c_void_p]
         if hasattr(L, "khb_check"):              # ABI 5
             L.khb_load_check_tables.argtypes = [C.c_void_p, P(CheckTables)]
             L.khb_check.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, P(CheckIn), C.c_uint32, P(CheckOut)]
@@ -213,6 +237,11 @@ def build_info(path: str | None = None) -> dict:
         info["sha16"] = hashlib.sha256(f.read()).hexdigest()[:16]
     info["path"] = path
     return info
+
+
+def kang_per_lane(path: str | None = None) -> int:
+    """Kangaroo slots per lane of the walk kernel (khb_kang_per_lane), a build-time constant."""
+    return int(lib(path).khb_kang_per_lane())
 
 
 def groups_per_item() -> int:
@@ -441,6 +470,55 @@ class Engine:
         out = C.create_string_buffer(n)
         _check(self.L.khb_vanity_match(self.h, bytes(h20), out, n), self.h, self.L)
         return out.raw
+
+    # ---- the kangaroo walk ----
+    def kang_load_jumps(self, jumps) -> None:
+        """The 32 jumps [(s_j, (x, y))], J_j = s_j * G (khhost.Kangaroo.jump_table)."""
+        if len(jumps) != 32:
+            raise ValueError("32 jumps")
+        dist = b"".join(s.to_bytes(32, "big") for s, _ in jumps)
+        xy = b"".join(x.to_bytes(32, "big") + y.to_bytes(32, "big") for _, (x, y) in jumps)
+        _check(self.L.khb_kang_load_jumps(self.h, dist, xy), self.h, self.L)
+
+    def kang_store(self, herd, first: int = 0) -> None:
+        """Kangaroos first .. of the herd from [(x, y, d)]; an empty list with first = 0 forgets the herd."""
+        xy = b"".join(x.to_bytes(32, "big") + y.to_bytes(32, "big") for x, y, _ in herd)
+        d = b"".join(d.to_bytes(32, "big") for _, _, d in herd)
+        _check(self.L.khb_kang_store(self.h, first, len(herd), xy or None, d or None), self.h, self.L)
+
+    def kang_herd(self) -> int:
+        return int(self.L.khb_kang_herd(self.h))
+
+    def kang_read(self, first: int = 0, n: int | None = None):
+        """[(x, y, d)] of kangaroos first .. first + n - 1 (to the herd's end by default)."""
+        n = self.kang_herd() - first if n is None else n
+        xy, d = C.create_string_buffer(64 * n), C.create_string_buffer(32 * n)
+        _check(self.L.khb_kang_read(self.h, first, n, xy, d), self.h, self.L)
+        f = int.from_bytes
+        return [(f(xy.raw[64 * i:64 * i + 32], "big"), f(xy.raw[64 * i + 32:64 * i + 64], "big"),
+                 f(d.raw[32 * i:32 * i + 32], "big")) for i in range(n)]
+
+    def kang_set_ring_capacity(self, cap: int) -> None:
+        _check(self.L.khb_kang_set_ring_capacity(self.h, cap), self.h, self.L)
+
+    def kang_submit(self, steps: int, dp_bits: int) -> None:
+        _check(self.L.khb_kang_submit(self.h, steps, dp_bits), self.h, self.L)
+
+    def kang_collect(self, cap: int | None = None):
+        """The oldest launch's distinguished points [(kangaroo, x, d)] (unordered, up to cap: the ring's capacity by
+        default) and its KangStats."""
+        cap = int(self.L.khb_kang_ring_capacity(self.h)) if cap is None else cap
+        out = (KangDp * max(cap, 1))()
+        st = KangStats()
+        _check(self.L.khb_kang_collect(self.h, out, cap, C.byref(st)), self.h, self.L)
+        n = min(st.n_dp, cap)
+        f = int.from_bytes
+        return [(out[i].kangaroo, f(bytes(out[i].x_be), "big"), f(bytes(out[i].dist_be), "big")) for i in range(n)], st
+
+    def kang_walk(self, steps: int, dp_bits: int, cap: int | None = None):
+        """One launch: kang_submit and kang_collect."""
+        self.kang_submit(steps, dp_bits)
+        return self.kang_collect(cap)
 
     # ---- -m minikeys ----
     def load_mini_table(self, points: bytes, window_bits: int) -> None:

@@ -12,9 +12,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libkhhost.so")
 _lib = None
 
 
-KHH_ABI_VERSION = 11                # include/khhost.h
+KHH_ABI_VERSION = 12                # include/khhost.h
 KHH_SESSION_STATS, KHH_ADDR_STATS = 12, 8
 KHH_MINI_STATS = 8
+KHH_KANG_STATS = 6
 MINI_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"   # Ccoinbuffer_default
 KHH_RESIDENT_INFO = 8
 TABLE_L1, TABLE_GATE, TABLE_FOLD, TABLE_STAGE0 = 0, 1, 2, 3      # include/khbsgs.h KHB_TABLE_*
@@ -145,6 +146,22 @@ def lib() -> C.CDLL:
         L.khh_mini_cpu_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, P(C.c_uint64), P(C.c_uint64)]
         L.khh_mini_search.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, P(C.c_int), C.c_int, C.c_uint32,
                                       C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, P(C.c_uint32),
+                                      P(C.c_uint64), C.c_uint32, C.c_char_p, C.c_size_t]
+        L.khh_kang_new.restype = C.c_void_p
+        L.khh_kang_new.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                   C.c_char_p, C.c_size_t]
+        L.khh_kang_free.argtypes = [C.c_void_p]
+        L.khh_kang_params.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint64), P(C.c_uint32)]
+        L.khh_kang_jumps.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.khh_kang_make_herd.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_char_p, C.c_char_p]
+        L.khh_kang_cpu_walk.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        P(C.c_uint32), C.c_char_p, C.c_char_p, C.c_uint64, P(C.c_uint64),
+                                        P(C.c_uint64)]
+        L.khh_kang_set_ring_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.khh_kang_plant.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64]
+        L.khh_kang_keep_herd.argtypes = [C.c_void_p, C.c_int]
+        L.khh_kang_final_herd.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, P(C.c_uint64)]
+        L.khh_kang_search.argtypes = [C.c_void_p, P(C.c_int), C.c_int, C.c_uint64, C.c_char_p, P(C.c_int),
                                       P(C.c_uint64), C.c_uint32, C.c_char_p, C.c_size_t]
         L.khh_addr_confirm.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int)]
         L.khh_hash160.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
@@ -751,6 +768,155 @@ class Minikeys:
                   rb[20 * i:20 * i + 20]) for i in range(n)]
         return found, {"candidates": st[0], "valid": st[1], "bad_keys": st[2], "hits": st[3], "launches": st[4],
                        "rescans": st[5], "filter_s": st[6] / 1e6, "keys_s": st[7] / 1e6}
+
+
+def _herd_bytes(herd) -> tuple[bytes, bytes]:
+    return (b"".join(_b32(x) + _b32(y) for x, y, _ in herd), b"".join(_b32(d) for _, _, d in herd))
+
+
+def _herd_list(xy: bytes, d: bytes, n: int) -> list[tuple[int, int, int]]:
+    f = int.from_bytes
+    return [(f(xy[64 * i:64 * i + 32], "big"), f(xy[64 * i + 32:64 * i + 64], "big"), f(d[32 * i:32 * i + 32], "big"))
+            for i in range(n)]
+
+
+class Kangaroo:
+    """Pollard's kangaroo interval search with distinguished points for one public key: the key of `pub` (x||y, 64
+    bytes) is sought in [start, end), 2^16 <= end - start <= 2^200.  Kangaroo i is tame for even i (its point is d*G)
+    and wild for odd i (Q + d*G, Q = P - start*G); a herd is a list of (x, y, d).  dp_bits and herd (kangaroos per
+    device) default to the largest with herd * 2^dp_bits <= 2^(w // 2 - 2), w the bit length of the width."""
+
+    def __init__(self, pub: bytes, start: int, end: int, dp_bits: int | None = None, herd: int | None = None,
+                 seed: int = 0):
+        err = C.create_string_buffer(256)
+        if not (0 <= start < 1 << 256 and 0 <= end < 1 << 256):
+            raise ValueError("the interval is start < end <= n")
+        self.h = lib().khh_kang_new(bytes(pub), _b32(start), _b32(end), -1 if dp_bits is None else dp_bits,
+                                    herd or 0, seed & ((1 << 64) - 1), 0, err, 256)
+        if not self.h:
+            raise ValueError(f"khh_kang_new: {err.value.decode()}")
+        dp, hd, w = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        lib().khh_kang_params(self.h, C.byref(dp), C.byref(hd), C.byref(w))
+        self.dp_bits, self.herd, self.width_bits = dp.value, hd.value, w.value
+        self.start, self.end = start, end
+        self._eng = None
+        self._ring = 0
+
+    def close(self) -> None:
+        if getattr(self, "_eng", None) is not None:
+            self._eng.close()
+            self._eng = None
+        if getattr(self, "h", None):
+            lib().khh_kang_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def jump_table(self) -> list[tuple[int, tuple[int, int]]]:
+        """The 32 jumps [(s_j, (x, y))] with (x, y) = s_j * G."""
+        d, xy = C.create_string_buffer(32 * 32), C.create_string_buffer(64 * 32)
+        lib().khh_kang_jumps(self.h, d, xy)
+        return [(s, (x, y)) for x, y, s in _herd_list(xy.raw, d.raw, 32)]
+
+    def make_herd(self, n: int | None = None, stream: int = 0) -> list[tuple[int, int, int]]:
+        """The first n kangaroos a search gives its device number `stream` (the whole herd by default)."""
+        n = self.herd if n is None else n
+        xy, d = C.create_string_buffer(64 * n), C.create_string_buffer(32 * n)
+        if lib().khh_kang_make_herd(self.h, stream, n, xy, d):
+            raise KhhError("khh_kang_make_herd")
+        return _herd_list(xy.raw, d.raw, n)
+
+    def cpu_walk(self, herd, steps: int, dp_bits: int | None = None):
+        """The step rule on the CPU (khh_kang_cpu_walk): (the herd after `steps` jumps each, the distinguished
+        points [(kangaroo, x, d)] in the order they are met, the number of second choices)."""
+        n = len(herd)
+        dp = self.dp_bits if dp_bits is None else dp_bits
+        xyb, db = _herd_bytes(herd)
+        xy, d = C.create_string_buffer(xyb, 64 * n), C.create_string_buffer(db, 32 * n)
+        cap = n * steps
+        idx = (C.c_uint32 * cap)()
+        px, pd = C.create_string_buffer(32 * cap), C.create_string_buffer(32 * cap)
+        ndp, sec = C.c_uint64(0), C.c_uint64(0)
+        if lib().khh_kang_cpu_walk(self.h, xy, d, n, steps, dp, idx, px, pd, cap, C.byref(ndp), C.byref(sec)):
+            raise ValueError("khh_kang_cpu_walk: a herd, steps >= 1 and dp_bits <= 32")
+        f = int.from_bytes
+        dps = [(idx[i], f(px.raw[32 * i:32 * i + 32], "big"), f(pd.raw[32 * i:32 * i + 32], "big"))
+               for i in range(ndp.value)]
+        return _herd_list(xy.raw, d.raw, n), dps, sec.value
+
+    # ---- the raw launch on one device (libkhbsgs through khbsgs.Engine) ----
+    def engine(self, device: int = 0):
+        """The device context of load_herd / read_herd / walk, opened on first use with the jump table loaded."""
+        if self._eng is None:
+            from .khbsgs import Engine
+            self._eng = Engine(device)
+            self._eng.kang_load_jumps(self.jump_table())
+            if self._ring:
+                self._eng.kang_set_ring_capacity(self._ring)
+        return self._eng
+
+    def load_herd(self, herd=None, device: int = 0) -> None:
+        """Replace the device's herd by [(x, y, d)] (make_herd() by default)."""
+        e = self.engine(device)
+        e.kang_store([], 0)
+        e.kang_store(self.make_herd() if herd is None else herd, 0)
+
+    def read_herd(self) -> list[tuple[int, int, int]]:
+        return self.engine().kang_read()
+
+    def walk(self, steps: int, dp_bits: int | None = None):
+        """One launch of `steps` jumps per kangaroo: ([(kangaroo, x, d)] unordered, stats dict)."""
+        dps, st = self.engine().kang_walk(steps, self.dp_bits if dp_bits is None else dp_bits)
+        return dps, {"steps_walked": st.steps_walked, "n_dp": st.n_dp, "second_choice": st.second_choice,
+                     "dp_overflow": st.dp_overflow, "kernel_ms": st.kernel_ms}
+
+    def set_ring_capacity(self, cap: int) -> None:
+        """Ring entries per launch, of walk() and of search() (0 = the search's own sizing; walk keeps its last)."""
+        lib().khh_kang_set_ring_capacity(self.h, cap)
+        self._ring = cap
+        if cap and self._eng is not None:
+            self._eng.kang_set_ring_capacity(cap)
+
+    # ---- test hooks of the search ----
+    def plant(self, herd) -> None:
+        """The first kangaroos of the first device's herd in the next searches."""
+        xy, d = _herd_bytes(herd)
+        if lib().khh_kang_plant(self.h, xy, d, len(herd)):
+            raise ValueError("plant: more kangaroos than the herd")
+
+    def keep_herd(self, keep: bool = True) -> None:
+        lib().khh_kang_keep_herd(self.h, int(keep))
+
+    def final_herd(self) -> list[tuple[int, int, int]]:
+        n = C.c_uint64(0)
+        lib().khh_kang_final_herd(self.h, None, None, 0, C.byref(n))
+        xy, d = C.create_string_buffer(64 * n.value), C.create_string_buffer(32 * n.value)
+        lib().khh_kang_final_herd(self.h, xy, d, n.value, C.byref(n))
+        return _herd_list(xy.raw, d.raw, n.value)
+
+    def search(self, devices=(0,), max_steps: int = 0) -> dict:
+        """{key | None, steps, dps, dead, lost_dps, launches, seconds}.  One herd per entry of `devices`; an empty
+        `devices` walks one herd on the CPU (cpu_walk's code).  max_steps: jumps in all, 0 = until found."""
+        devs = (C.c_int * max(len(devices), 1))(*devices)
+        key, found = C.create_string_buffer(32), C.c_int(0)
+        st = (C.c_uint64 * KHH_KANG_STATS)()
+        err = C.create_string_buffer(256)
+        rc = lib().khh_kang_search(self.h, devs, len(devices), max_steps, key, C.byref(found), st, KHH_KANG_STATS,
+                                   err, 256)
+        if rc:
+            raise KhhError(f"khh_kang_search: {err.value.decode()} [{rc}]")
+        return {"key": int.from_bytes(key.raw, "big") if found.value else None, "steps": st[0], "dps": st[1],
+                "dead": st[2], "lost_dps": st[3], "launches": st[4], "seconds": st[5] / 1e6}
 
 
 def resident_gate_log2(l1ext: int, budget_bytes: int) -> int:
