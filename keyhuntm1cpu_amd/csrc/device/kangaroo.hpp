@@ -110,7 +110,9 @@ __device__ __forceinline__ void kang_step(const KangArgs& A, const KangJumpLds& 
     }
     aff_add(P, P, J, is);
     const Fe sj = kang_jump_fe(jt, j, 16);
-    fm_add8(dist.v, dist.v, sj.v);           // cannot wrap for the accepted widths
+    // a plain add through all eight words: a carry out of the top is dropped, so the distance is kept mod 2^256, as
+    // the model's and the host's is (the accepted widths never get there; test_gpu_kangaroo_directed.py pins the wrap)
+    fm_add8(dist.v, dist.v, sj.v);
     X[s * S] = P.x;
     Y[s * S] = P.y;
     D[s * S] = dist;

@@ -268,6 +268,7 @@ class Engine:
         self.h = C.c_void_p()
         _check(self.L.khb_open(device, lanes, C.byref(self.h)), None, self.L)
         self.gpl = 0
+        self._kang_rings: list[int] = []                 # ring capacities of the kangaroo launches in flight
 
     def close(self) -> None:
         if self.h:
@@ -502,16 +503,22 @@ class Engine:
         _check(self.L.khb_kang_set_ring_capacity(self.h, cap), self.h, self.L)
 
     def kang_submit(self, steps: int, dp_bits: int) -> None:
+        ring = int(self.L.khb_kang_ring_capacity(self.h))
         _check(self.L.khb_kang_submit(self.h, steps, dp_bits), self.h, self.L)
+        self._kang_rings.append(ring)                    # the launch keeps the capacity it was submitted with
 
     def kang_collect(self, cap: int | None = None):
-        """The oldest launch's distinguished points [(kangaroo, x, d)] (unordered, up to cap: the ring's capacity by
-        default) and its KangStats."""
-        cap = int(self.L.khb_kang_ring_capacity(self.h)) if cap is None else cap
+        """The oldest launch's distinguished points [(kangaroo, x, d)] (unordered, up to cap: the capacity of that
+        launch's ring by default) and its KangStats."""
+        ring = self._kang_rings[0] if self._kang_rings else int(self.L.khb_kang_ring_capacity(self.h))
+        cap = ring if cap is None else cap
         out = (KangDp * max(cap, 1))()
         st = KangStats()
-        _check(self.L.khb_kang_collect(self.h, out, cap, C.byref(st)), self.h, self.L)
-        n = min(st.n_dp, cap)
+        rc = self.L.khb_kang_collect(self.h, out, cap, C.byref(st))
+        if rc != KHB_ESTATE and self._kang_rings:        # the launch is retired whatever else the call answers
+            self._kang_rings.pop(0)
+        _check(rc, self.h, self.L)
+        n = min(st.n_dp, cap, ring)                      # what the ring kept: the counter goes on past its capacity
         f = int.from_bytes
         return [(out[i].kangaroo, f(bytes(out[i].x_be), "big"), f(bytes(out[i].dist_be), "big")) for i in range(n)], st
 

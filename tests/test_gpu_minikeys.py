@@ -188,7 +188,67 @@ def test_hit_ring_overflow_is_rescanned(eng, ora, targets):
     assert (st["candidates"], st["valid"]) == (count, nvalid) and st["rescans"] >= 1
 
 
-# ---------------------------------------------------------------------------------------------- 5: errors
+# ---------------------------------------------------------------------------------------------- 5: long runs
+# Every test above opens 16,384 lanes, where a filter lane's run is the minimum of 64 and the keys kernel never makes a
+# second pass.  With 256 lanes the filter has 1,024 lanes and the keys kernel one block, so spans of a few million
+# candidates reach the run lengths of a production launch (hundreds to 4,096, the clamp) against tests/mini_ref.py's
+# block-wise enumerator.
+FILTER_LANES = 4 * 256
+RUN_SPANS = [(262_144, 256), (FILTER_LANES * 600 + 17, 601), (FILTER_LANES * 3400, 3400)]
+
+
+@pytest.fixture(scope="module")
+def small():
+    e = khbsgs.Engine(0, lanes=256)
+    assert e.lanes() == 256
+    yield e
+    e.close()
+
+
+def _run(count):
+    return min(4096, max(64, -(-count // FILTER_LANES)))
+
+
+@pytest.mark.parametrize("count,run", RUN_SPANS, ids=["run-256", "run-601-ragged", "run-3400"])
+def test_filter_run_lengths(small, count, run):
+    """Runs of 256 (four d20 wraps each, most lanes starting mid-run), 601 with a ragged last lane, and 3,400: above
+    58^2 = 3,364, so every lane repacks its head once and some twice."""
+    assert _run(count) == run
+    ref = [o for o in mr.valid_offsets_fast(mr.A, RUN_SPANS[-1][0]) if o < count]
+    assert len(mr.valid_offsets_fast(mr.A, RUN_SPANS[-1][0])) == 13_332
+    got, n = small.mini_filter(_digits(mr.A), count)
+    assert n == len(ref) == len(got)
+    assert sorted(got) == ref
+
+
+def test_filter_run_clamp(small):
+    """The run clamped at 4,096: more blocks than 4 * lanes / 256, a ragged tail, and the carry through 20 digits (six
+    candidates in) inside the first lane's run."""
+    count = FILTER_LANES * 4096 + 4096 * 3 + 5
+    assert -(-count // FILTER_LANES) > 4096 == _run(count) and -(-count // 4096) == FILTER_LANES + 4
+    ref = mr.valid_offsets_fast(mr.B, count)
+    got, n = small.mini_filter(_digits(mr.B), count)
+    assert n == len(ref) == len(got)
+    assert sorted(got) == ref
+
+
+def test_keys_kernel_second_pass(small, ora, targets):
+    """275 survivors against the 256 lanes of the keys kernel's one block: 19 of them come from a second pass of its
+    grid-stride loop.  Every survivor is planted, so each must come back once with the oracle's hash160."""
+    first, count, nvalid = mr.SPANS[3]
+    offs = mr.valid_offsets_fast(first, count)
+    assert len(offs) == nvalid == 275 > small.lanes()
+    pl = _planted(ora, first, offs)
+    _load(small, _text(targets, pl), w=8)
+    hits, st = small.mini_scan(_digits(first), count)
+    assert (st.candidates, st.valid, st.hits, st.bad_keys) == (count, 275, 275, 0)
+    assert (st.queue_overflow, st.hit_overflow) == (0, 0)
+    assert len(hits) == 275 and sorted(o for o, _ in hits) == offs
+    for o, h in hits:
+        assert h == pl[o][2]
+
+
+# ---------------------------------------------------------------------------------------------- 6: errors
 def test_errors_launch_nothing(targets):
     last = "S" + "z" * 21
     with khbsgs.Engine(0, lanes=16384) as e:

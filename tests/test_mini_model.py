@@ -38,3 +38,19 @@ def test_span_counts(first, count, want):
     offs = mr.valid_offsets(first, count)
     assert len(offs) == want
     assert offs == sorted(set(offs)) and all(0 <= o < count for o in offs)
+
+
+def test_fast_enumerator_agrees():
+    """valid_offsets_fast against the candidate-by-candidate model: SPANS[3] (20 blocks of 58^2 from mid-block), the
+    span that carries through 20 digits, another alphabet, a span inside one block and a prefix cut from the cache."""
+    first, count, want = mr.SPANS[3]
+    ref = mr.valid_offsets(first, count)
+    assert mr.valid_offsets_fast(first, count) == ref and len(ref) == want
+    assert mr.valid_offsets_fast(first, 10109) == mr.valid_offsets(first, 10109)      # cut from the longer one
+    first, count, want = mr.SPANS[4]
+    assert mr.valid_offsets_fast(first, count) == mr.valid_offsets(first, count)
+    rev = mr.ALPHABET[::-1]
+    first = mr.string(mr.value(mr.SPANS[0][0]), rev)
+    assert mr.valid_offsets_fast(first, 10109, rev) == mr.valid_offsets(first, 10109, rev)
+    inside = mr.step(mr.A, 58 * 58 + 7)
+    assert mr.valid_offsets_fast(inside, 3000) == mr.valid_offsets(inside, 3000)
